@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the PPT hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line; everything else it can measure (below: roofline,
+parity_mode, split16_mode, parity, cpu_baseline, secondary, the multi-rank all-reduce alone) runs only with --full.
+--dump-outputs DIR writes what the timed path returned in its last timed step (dump_outputs below).  The inputs are seeded, and
+such a run fixes the burn-in's step count and runs the input stages in order (main; with --eval it injects fixed FPS starts,
+main_eval), so that it computes the same from run to run: two builds run with the same arguments can be compared output for output.
 
 Workload (BASELINE.json configs[1], "C2"): ModelNet40 class list, 1024-point clouds, PointBERT
 (ULIP_PointBERT, head_type=0: frozen backbone + PromptLearner), batch 32 PER GPU, model.train()
@@ -14,7 +20,7 @@ Timing: BURN_IN_STEPS (40) untimed steps (clock ramp-up, hipGraph capture; repor
 untimed steps, then EXACTLY --steps K steps bracketed by barrier + torch.cuda.synchronize(): `value` = clouds / that
 time; "ms_per_step_median" is the median of the K per-step times taken with HIP events on the caller's stream.
 
-Prints ONE JSON line (rank 0): metric/value/unit..., plus
+Prints ONE JSON line (rank 0): metric/value/unit..., plus with --full
   "roofline":     the dominant kernel (the 16-bit -- fp16 / bf16 -- MFMA GEMM family) -- algorithmic FLOPs / its summed launch
                   time measured with HIP events on the launch stream during a second, instrumented pass
                   over the same K steps -- against the 2.5 PFLOP/s dense bf16 peak;
@@ -24,7 +30,8 @@ Prints ONE JSON line (rank 0): metric/value/unit..., plus
   "split16_mode": ... and in the split16 mode (fp32 storage, products from hi + lo half pairs on the 16-bit matrix pipe: the fp32
                   mode's parity bounds at ~2x its rate);
   "cpu_baseline": the oracle (CPU restatement of the reference, `kind: "port"`) timed on this host's cores
-                  on the reference's CPU-runnable case C1 (batch 8), rank 0, N=1 only.
+                  on the reference's CPU-runnable case C1 (batch 8), rank 0, N=1 only;
+  "secondary":    short runs of the other configurations as child processes (secondary_runs), C2 at N = 1 only.
 """
 import argparse
 import json
@@ -249,6 +256,28 @@ def host_feed(tensors, steps):
     return iter(DevicePrefetcher((host for _ in range(steps)), depth=2))
 
 
+DUMP_BYTES = 64 << 20             # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: one DIR/<name>.npy per array the timed path handed its caller in its last timed step, as float32
+    (float64 stays float64).  Should they exceed DUMP_BYTES in all, every array over an equal share of it is written as
+    DIR/<name>_sample.npy instead: its elements at a fixed, seeded set of flat positions (sorted), the same in every run."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        arrs[name] = (t.double() if t.dtype == torch.float64 else t.float()).numpy()
+    share = DUMP_BYTES // max(1, len(arrs))
+    over = sum(x.nbytes for x in arrs.values()) > DUMP_BYTES
+    for name, x in arrs.items():
+        if over and x.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False))
+            np.save(os.path.join(path, name + "_sample.npy"), x.reshape(-1)[keep])
+        else:
+            np.save(os.path.join(path, name + ".npy"), x)
+
+
 FEED = os.environ.get("PPT_BENCH_FEED", "resident")
 WEIGHTS = os.environ.get("PPT_BENCH_WEIGHTS", "synthetic")    # "ckpt_like": ppt_amd.weights.checkpoint_like magnitudes (secondary leg)
 BENCH_MODE = os.environ.get("PPT_BENCH_MODE", "mixed16")      # "split16": the step in the split16 precision mode (secondary legs)
@@ -321,9 +350,13 @@ def main_eval(a):
     model.eval()
     # the synthetic batch is resident and complete before every call: the next batch's grouping / tokenizer stage may start
     # when forward() is called (ULIP_WITH_IMAGE.eval_inputs_ready; PPT_EVAL_AHEAD=0 for the in-order forward)
-    model.eval_inputs_ready = os.environ.get("PPT_EVAL_AHEAD", "1") != "0" and FEED != "prefetch"
+    model.eval_inputs_ready = os.environ.get("PPT_EVAL_AHEAD", "1") != "0" and FEED != "prefetch" and not a.dump_outputs   # (see main)
     B, N = cfg["batch"], cfg["npoints"]
     pc = torch.from_numpy(W.synth_clouds(B, N, seed=1234)[0]).cuda()
+    if a.dump_outputs and cfg.get("model", "ULIP_PointBERT") == "ULIP_PointBERT":
+        # --dump-outputs: one FPS start per cloud drawn once from a seed and injected (the tower's hook), the same in every call.  Drawn
+        # inside the hipGraph, they differ between two runs even with the input stages in order (measured on C2: 1.3 in the logits).
+        model.point_encoder.fps_start = torch.from_numpy(np.random.default_rng(0).integers(0, N, size=B)).cuda()
     extra = ()
     if cfg.get("task") == "partseg":
         extra = (torch.nn.functional.one_hot(torch.arange(B) % 16, 16).float().cuda(),)
@@ -338,6 +371,8 @@ def main_eval(a):
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
     assert torch.isfinite(logits).all()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"logits": logits})
     out = {"metric": METRICS[a.config].replace("fwd+bwd", "validate() forward"), "value": round(B * a.steps / dt, 2),
            "unit": "point-clouds/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "burn_in": BURN_IN_STEPS,
            "ms_per_step": round(1e3 * dt / a.steps, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -454,11 +489,15 @@ def main():
     ap.add_argument("--eval", action="store_true", help="validate() throughput (main_cls.py:237-299): eval-mode forward under "
                     "no_grad, text features cached, no backward / optimizer")
     ap.add_argument("--parity", action="store_true", help="measure the parity triple against the golden fixture even when --no-parity-mode "
-                    "skips the fp32 / split16 mode runs (the ckpt_like secondary leg)")
+                    "or a run without --full skips the fp32 / split16 mode runs (the ckpt_like secondary leg)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the short C3 / C4 / C5 / eval runs reported under `secondary`")
+    ap.add_argument("--full", action="store_true", help="also measure everything besides the headline figure: roofline, parity_mode, "
+                    "split16_mode, parity, cpu_baseline, secondary (each can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path returned in its last timed step as DIR/<name>.npy")
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        return launch_ranks(a.gpus, sys.argv[1:])        # (before ANY GPU call of this process)
+        argv = sys.argv[1:] + (["--dump-outputs", os.path.abspath(a.dump_outputs)] if a.dump_outputs else [])   # (ranks run in ROOT)
+        return launch_ranks(a.gpus, argv)        # (before ANY GPU call of this process)
     if os.environ.get("PPT_BENCH_DRY") == "gloo":
         return main_dry(a)
     if a.eval:
@@ -477,6 +516,10 @@ def main():
     c_ = CONFIGS[a.config]
     group_ahead = GROUP_AHEAD and (frozen_too or (c_["head_type"] > 0 and c_.get("model", "ULIP_PointBERT") == "ULIP_PointBERT")
                                    or c_.get("model") in ("ULIP_PN_MSG", "ULIP_PN_MLP", "ULIP_PointBERT_partseg"))
+    # --dump-outputs: the input stages run in order.  Ahead, the random draws come from hipGraphs replayed on two streams (FPS starts on
+    # the grouping stream, DropPath on the caller's) that share the generator's state, and two runs differ from the first steps on
+    # (measured on C2: 41 steps apart by 0.04 in the logits; in order, or with hipGraphs off, two runs are bit-identical).
+    group_ahead = group_ahead and not a.dump_outputs
     if group_ahead:                    # (only where Trainer uses it: an extra stream shifts the others' queue positions)
         graphs.shared_group_stream()
     force_dist = os.environ.get("PPT_FORCE_DIST") == "1"      # exercise the RCCL path with a single rank (dev aid)
@@ -526,8 +569,9 @@ def main():
     import gc
     gc_mode = os.environ.get("PPT_BENCH_GC", "freeze")
     # (under a process group every step carries a collective, so every rank must run the SAME number of steps: the burn-in is then a
-    # fixed count -- what one second amounts to at this configuration's single-GPU rate would differ from rank to rank)
-    fixed_burn = BURN_IN_STEPS + int(os.environ.get("PPT_BENCH_BURN_IN_DIST", "320")) if (world > 1 or force_dist) else None
+    # fixed count -- what one second amounts to at this configuration's single-GPU rate would differ from rank to rank).  So it is
+    # with --dump-outputs: the state the last timed step starts from (AdamW's updates, the RNG's draws) must not depend on the clock.
+    fixed_burn = BURN_IN_STEPS + int(os.environ.get("PPT_BENCH_BURN_IN_DIST", "320")) if (world > 1 or force_dist or a.dump_outputs) else None
     burned, tb = 0, time.perf_counter()
     while (burned < fixed_burn) if fixed_burn is not None else \
             (burned < BURN_IN_STEPS or (time.perf_counter() - tb < burn_s and burned < max_burn)):
@@ -560,7 +604,7 @@ def main():
     marks[0].record()
     host_s[0] = t0
     for i in range(a.steps):
-        loss, _ = trainer.step(*(next(feed) if feed else (pc, label)))
+        loss, pred = trainer.step(*(next(feed) if feed else (pc, label)))
         marks[i + 1].record()
         host_s[i + 1] = time.perf_counter()
     trainer.finish()                         # (the deferred BatchNorm-buffer broadcast of a multi-rank run is timed too)
@@ -588,6 +632,7 @@ def main():
         per_rank = [1e3 * float(x.item()) / a.steps for x in every]
         elapsed = max(float(x.item()) for x in every)
         timing["ms_per_step_per_rank"] = {"min": round(min(per_rank), 3), "max": round(max(per_rank), 3)}
+    if (world > 1 or force_dist) and a.full:
         # the step's ONE collective, alone: the all-reduce of the flat gradient buffer (64 KiB at head_type 0) back to back on an
         # otherwise idle GPU, barrier-bracketed -- its latency over xGMI, which in the step overlaps the next point tower
         buf = trainer.sync.flat
@@ -602,9 +647,13 @@ def main():
         timing["allreduce_bytes"] = buf.numel() * 4
     final_loss = loss.item()
     assert np.isfinite(final_loss), "loss is not finite"
+    if rank == 0 and a.dump_outputs:
+        # (before the --full passes below, which train on: the loss and logits of the last timed step, the trained tensors after it)
+        dump_outputs(a.dump_outputs, dict({"loss": loss, "logits": pred},
+                                          **{"param." + n: p for n, p in model.named_parameters() if p.requires_grad}))
 
     roof = None
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         # further passes over the same K steps with every launch of the hot kernels bracketed by HIP events.  These
         # passes run eagerly (no hipGraph replay: events cannot be recorded inside one) and the host, slowed by two
         # event records per launch, falls behind the GPU, so how much of the text stream happens to overlap the point
@@ -693,16 +742,16 @@ def main():
                           "gradient_self_check": ({k: (round(v, 5) if isinstance(v, float) else v) for k, v in trainer.grad_calibration.items()}
                                                   if trainer.grad_calibration and trainer.grad_calibration.get("checked") else None)},
                "roofline": roof}
-        if world == 1 and not force_dist and not a.no_parity_mode:
+        if world == 1 and not force_dist and a.full and not a.no_parity_mode:
             out["parity_mode"] = parity_mode_rate(cfg, pc, label, trainer.extra_inputs, max(3, a.steps // 2), like=trainer)
             out["split16_mode"] = parity_mode_rate(cfg, pc, label, trainer.extra_inputs, max(3, a.steps // 2), mode="split16", like=trainer)
             if a.config == "C2":
                 out["parity"] = measured_parity()
         elif world == 1 and a.parity and a.config == "C2":
             out["parity"] = measured_parity()
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
-        if world == 1 and not force_dist and a.config == "C2" and not a.no_secondary:
+        if world == 1 and not force_dist and a.config == "C2" and a.full and not a.no_secondary:
             out["secondary"] = secondary_runs()
     if world > 1 or force_dist:
         dist.barrier()                       # rank 0 spends a few seconds more (roofline passes): tear down together

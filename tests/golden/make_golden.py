@@ -5,8 +5,8 @@ inputs and weights (ppt_amd.weights).  Build container only; the fixtures (data:
 regenerated from seeds, expected outputs are stored) are committed, this script documents
 how they were made.
 
-    python tests/golden/make_golden.py            # rewrites tests/golden/*.npz and
-                                                  # ppt_amd/data/classnames.json
+    python tests/golden/make_golden.py            # rewrites tests/golden/*.npz, tests/golden/bpe_merges_subset.txt.gz
+                                                  # and ppt_amd/data/classnames.json
 
 While generating, every oracle function (oracle/oracle.py, oracle/ppt_oracle.c) is checked
 against the reference output; the script aborts if the oracle is off.
@@ -65,6 +65,46 @@ def gen_tokens():
     with open(os.path.join(ROOT, "ppt_amd", "data", "classnames.json"), "w") as f:
         json.dump(out, f, indent=0)
     return out
+
+
+# The strings tests/test_tokenizer_cpu.py encodes besides the class names of classnames.json (add any new one here).
+BPE_TEXTS = ["X", ".", "a photo of a cat", "A  Photo\nof a CAT", "&amp;amp;", "&", "it's 42 tables, isn't it?", "a chair",
+             "a table", "chair", "rocking horse", "lamp (floor)", "zebra crossing", "lamp (floor).", "zebra crossing."]
+
+
+def gen_bpe_subset():
+    """tests/golden/bpe_merges_subset.txt.gz: the CLIP merge table (1.3 MB, over the size of a committed file) cut down to
+    what the tokenizer tests encode.  BPE on a piece only ever applies merges whose result is a substring of the piece (with
+    its end-of-word mark), so every such merge keeps its line -- and with it its rank and its vocabulary id; every other line
+    becomes a placeholder pair that can never match (its first symbol is no byte symbol) and whose token is unique."""
+    import gzip
+    from ppt_amd import tokenizer as T
+    full = os.path.join(R.REF_ROOT, "utils", T.VOCAB_FILE)
+    tk = T.SimpleTokenizer(full)
+    names = list(json.load(open(os.path.join(ROOT, "ppt_amd", "data", "classnames.json")))["name_tokens"])
+    texts = names + [n + "." for n in names] + BPE_TEXTS
+    words = set()
+    for t in texts:
+        for piece in T._SPLIT.findall(tk.clean(t)):
+            words.add("".join(tk.byte_sym[b] for b in piece.encode("utf-8")) + T.END)
+    with gzip.open(full, "rt", encoding="utf-8") as f:
+        lines = f.read().split("\n")
+    out, kept = [lines[0]], 0
+    for i, line in enumerate(lines[1:1 + T.N_MERGES]):
+        a, b = line.split()
+        if any(a + b in w for w in words):
+            out.append(line)
+            kept += 1
+        else:
+            out.append(f"␀ {i}")
+    path = os.path.join(HERE, "bpe_merges_subset.txt.gz")
+    with gzip.GzipFile(path, "wb", mtime=0) as f:          # (mtime 0: the same bytes on every run)
+        f.write("\n".join(out).encode("utf-8"))
+    sub = T.SimpleTokenizer(path)
+    for t in texts:
+        assert sub.encode(t) == tk.encode(t), t
+        assert sub(t).tolist() == tk(t).tolist(), t
+    print(f"bpe subset: {kept} of {T.N_MERGES} merges kept, {os.path.getsize(path)} bytes")
 
 
 def gen_index():
@@ -608,6 +648,8 @@ if __name__ == "__main__":
         gen_pointmlp()
     elif sys.argv[1:] == ["index"]:
         gen_index()
+    elif sys.argv[1:] == ["bpe"]:
+        gen_bpe_subset()
     elif sys.argv[1:] == ["blocks"]:
         gen_blocks(gen_tokens())
     elif sys.argv[1:2] == ["steps"]:            # the train-step fixtures of the given head_types only
@@ -616,6 +658,7 @@ if __name__ == "__main__":
         gen_encoder_and_step(gen_tokens(), tuple(int(h) for h in sys.argv[2:]) or (0, 3), profile="ckpt")
     else:
         tok = gen_tokens()
+        gen_bpe_subset()
         gen_index()
         gen_encoder_and_step(tok)
         gen_encoder_and_step(tok, (0, 3), profile="ckpt")

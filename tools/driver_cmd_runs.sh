@@ -12,6 +12,6 @@ i, t0, t1 = sys.argv[1], float(sys.argv[2]), float(sys.argv[3])
 d = json.loads(open(f"gpurun_out/r6_final_driver_cmd_{i}.json").read().strip().splitlines()[-1])
 t = d["config"]["timing"]
 sec = {k: (v.get("value") if isinstance(v, dict) else v) for k, v in d.get("secondary", {}).items()}
-print(f"run {i}: wall {t1 - t0:.0f} s | {d['value']} clouds/s {d['ms_per_step']} ms (median {t.get('ms_per_step_median')}, max {t.get('ms_per_step_max')}) roofline {d['roofline']['frac']} | {sec}")
+print(f"run {i}: wall {t1 - t0:.0f} s | {d['value']} clouds/s {d['ms_per_step']} ms (median {t.get('ms_per_step_median')}, max {t.get('ms_per_step_max')}) roofline {(d.get('roofline') or {}).get('frac')} | {sec}")
 PY
 done

@@ -50,7 +50,7 @@ def section(rnd, cfg, d, out):
     roof = bench.get("roofline") or {}
     par = bench.get("parity_mode") or {}
     md = [f"## {cfg.upper()} -- {bench['config']['workload']}", "",
-          f"`{rnd}_bench_{cfg}.json`: `python bench.py --config {cfg.upper()}` -> **{bench['value']} clouds/s**, {bench['ms_per_step']} ms/step "
+          f"`{rnd}_bench_{cfg}.json`: `python bench.py --full --config {cfg.upper()} --no-secondary` -> **{bench['value']} clouds/s**, {bench['ms_per_step']} ms/step "
           f"(median step {bench.get('ms_per_step_median')} ms; {bench['steps']} steps after {bench.get('burn_in')} burn-in + {bench['warmup']} warm-up)"
           + (f"; fp32 parity mode {par.get('value')} clouds/s ({par.get('ms_per_step')} ms/step)" if par else "") + ".", "",
           f"roofline (16-bit MFMA GEMM family, HIP-event brackets in an eager pass): {roof.get('achieved')} TFLOP/s = {100 * (roof.get('frac') or 0):.1f} % of 2.5 "

@@ -15,7 +15,7 @@ for C in $CFGS; do
     # moves part segmentation to split16 (round 6), and that number is in the C2 line's `secondary.C5` / `C5_split16`.  (exported
     # here, in the shell: nothing but the program itself may follow rocprofv3's `--`)
     if [ "$C" = C5 ]; then export PPT_GRAD_CHECK=off; else unset PPT_GRAD_CHECK; fi
-    python3 "$ROOT/bench.py" --config "$C" --no-secondary > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err"
+    python3 "$ROOT/bench.py" --full --config "$C" --no-secondary > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err"
     tail -c 400 "$OUT/bench_$c.json"; echo
     rm -rf "$OUT/trace_$c"
     rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$c" -o p -- python3 "$ROOT/bench.py" --config "$C" --steps 10 --warmup 5 \
