@@ -46,7 +46,8 @@ const char *ppt_strerror(int code);
  *    the workgroups that did), ppt_vit_mlp3_bf16 / ppt_vit_mlp3_retile (new: csrc/mlp_fused3.hip), ppt_text_mlp_pair /
  *    ppt_text_mlp_retile (new: csrc/text_mlp.hip), ppt_lnlin / ppt_lnlin_retile (new: csrc/lnlin.hip),
  *    ppt_text_mlp_retile_split + the split16 fields of ppt_text_mlp_params (csrc/text_mlp_split.hip), ppt_text_lin_split /
- *    ppt_text_lin_retile_split (csrc/text_lin_split.hip).
+ *    ppt_text_lin_retile_split (csrc/text_lin_split.hip); later, additive only (no existing signature or struct changed):
+ *    ppt_text_lin16 / ppt_text_lin_retile16 (the 16-bit form of ppt_text_lin_split).
  * 6: ppt_gemm_params.split16 / split_a_pow2 / split_b_pow2 (new trailing fields: fp32 operands as hi + lo half pairs),
  *    ppt_attention_fwd_split16 / ppt_attention_bwd_split16 (new), ppt_pointmlp_cloud_rstd / ppt_pointmlp_pq (new).
  * 5: ppt_labels_check (new), ppt_gemm256 (new: the 256-row macro-tile GEMM core), ppt_set_gemm256 / ppt_get_gemm256 (new),
@@ -385,6 +386,24 @@ typedef struct ppt_text_lin_params {
 } ppt_text_lin_params;
 int ppt_text_lin_retile_split(const float *W, void *W_tiled, int N, int K, int b_pow2, void *stream);
 int ppt_text_lin_split(const ppt_text_lin_params *p, void *stream);
+/* ... and its form on the mixed mode's 16-bit operands (ABI 7, additive; csrc/text_lin_split.hip): C[M, N] = A[M, K] W[N, K]^T
+ * (+ bias) (+ residual), one MFMA per 16-bit fragment, fp32 accumulation.  C is fp32 (c_dtype PPT_F32) or `dtype` (rounded as
+ * ppt_gemm rounds: beyond the format's range is +-inf).  K a multiple of 512, N of 256; K > 512: the K chunks' fp32 partial products
+ * parts[K / 512][M][N] (c_dtype PPT_F32, ldc == N, no bias / residual).  W: the fragment-ordered copy of ppt_text_lin_retile16
+ * (N * K * 2 bytes) of the 16-bit [N, K] weight. */
+typedef struct ppt_text_lin16_params {
+    const void *A; int64_t lda;              /* dtype [M, K] */
+    const void *W;
+    const float *bias;                       /* [N] or NULL */
+    const float *residual; int64_t ld_res;   /* fp32 [M, N] or NULL */
+    void *C; int64_t ldc;                    /* c_dtype [M, N] */
+    int M, N, K;
+    int dtype;                               /* PPT_F16 | PPT_BF16 */
+    int c_dtype;                             /* PPT_F32 or dtype */
+    int wave_prio;                           /* != 0: raised issue priority (0: what ppt_set_wave_priority set) */
+} ppt_text_lin16_params;
+int ppt_text_lin_retile16(const void *W, void *W_tiled, int N, int K, void *stream);
+int ppt_text_lin16(const ppt_text_lin16_params *p, void *stream);
 
 /* ---- Attention ---------------------------------------------------------------------------------
  * softmax(scale * q k^T [+ causal mask]) v per (batch, head).  Replaces

@@ -7,3 +7,18 @@ import os
 # Eight queues keep them apart.  Must be set before the HIP runtime initialises, i.e. import ppt_amd (or bench.py)
 # before the first torch.cuda call; an explicit GPU_MAX_HW_QUEUES in the environment wins.
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+
+
+# A forked child (the DataLoader's workers: ppt_amd/data/fps_service.py) inherits the parent's whole Python heap, including
+# garbage cycles that still hold HIP objects -- graphs, events, streams of models that are gone (the hazard graphs.GraphedCall
+# guards its captures against).  Should the child's cyclic collector run before the parent's has, it finalises them, and a HIP
+# call in a forked process faults ("Fatal Python error: Segmentation fault ... Garbage-collecting" in the worker's bootstrap,
+# whenever an allocation count happened to put a collection there).  The child therefore moves everything it inherited into the
+# collector's permanent generation: its own new objects are collected as usual, the parent's are never finalised by it.
+def _freeze_inherited_heap():
+    import gc
+    gc.freeze()
+
+
+if hasattr(os, "register_at_fork"):
+    os.register_at_fork(after_in_child=_freeze_inherited_heap)

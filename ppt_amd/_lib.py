@@ -51,6 +51,15 @@ class TextLinParams(ctypes.Structure):
     ]
 
 
+class TextLin16Params(ctypes.Structure):
+    """struct ppt_text_lin16_params (include/ppt_hip.h) -- field order must match the header."""
+    _fields_ = [
+        ("A", c_void_p), ("lda", c_int64), ("W", c_void_p), ("bias", c_void_p), ("residual", c_void_p), ("ld_res", c_int64),
+        ("C", c_void_p), ("ldc", c_int64), ("M", c_int), ("N", c_int), ("K", c_int), ("dtype", c_int), ("c_dtype", c_int),
+        ("wave_prio", c_int),
+    ]
+
+
 class TextMlpParams(ctypes.Structure):
     """struct ppt_text_mlp_params (include/ppt_hip.h) -- field order must match the header."""
     _fields_ = [
@@ -136,6 +145,8 @@ _SIGNATURES = {
     "ppt_text_mlp_retile_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "ppt_text_lin_retile_split": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ppt_text_lin_split": (c_int, [ctypes.POINTER(TextLinParams), c_void_p]),
+    "ppt_text_lin_retile16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "ppt_text_lin16": (c_int, [ctypes.POINTER(TextLin16Params), c_void_p]),
     "ppt_vit_mlp3_retile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ppt_vit_mlp3_bf16": (c_int, [ctypes.POINTER(VitMlpParams), c_void_p]),
     "ppt_rowgemm_bf16": (c_int, [ctypes.POINTER(RowGemmParams), c_void_p]),

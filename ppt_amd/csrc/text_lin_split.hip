@@ -1,16 +1,19 @@
-// text_lin_split.hip -- round 6: ONE linear of the CLIP text tower's attention half on split16 products (fp32 operands multiplied as
-// hi + lo IEEE-half pairs, gemm_common.h), rows stationary and the weight streamed -- the first product of csrc/text_mlp_split.hip as a
-// launch of its own.  On the prompt chain (817 rows with the shared prefix) these are in_proj (512 -> 1536), out_proj (512 -> 512,
-// + bias + residual) and their two input-gradient products (512 -> 512; 1536 -> 512 as three K chunks whose partial products the
-// LayerNorm backward adds up, as it did for the split-K tile GEMM): 48 of the chain's 96 split16 tile GEMMs of ~20 us each -- 64 x 64
-// tiles whose K loop pays a global round trip, a split and a barrier per 32 k.
+// text_lin_split.hip -- ONE linear of the CLIP text tower's attention half, rows stationary and the weight streamed -- the first
+// product of csrc/text_mlp_split.hip / csrc/text_mlp.hip as a launch of its own.  On the prompt chain (817 rows with the shared
+// prefix) these are in_proj (512 -> 1536), out_proj (512 -> 512, + bias + residual) and their two input-gradient products
+// (512 -> 512; 1536 -> 512 as three K chunks whose partial products the LayerNorm backward adds up, as it did for the split-K tile
+// GEMM): 48 of the chain's tile GEMMs per step -- 64 x 64 tiles whose K loop pays a global round trip and a barrier per 32 k.
 //
+// Two operand forms of one kernel template (FORM):
+//   * PPT_F32 (round 6, split16): fp32 operands multiplied as hi + lo IEEE-half pairs (gemm_common.h), three MFMAs per fragment pair;
+//   * PPT_F16 / PPT_BF16 (round 7): the 16-bit operands of the mixed mode as they are, one MFMA per fragment.
 // A workgroup = a 32-row block x a slice of SLN output columns x one 512-wide K chunk:
-//   * the block's rows of A (fp32, columns [512 c, 512 c + 512)) are multiplied by 2^a_pow2, saturated to half's range (counted),
-//     split ONCE and kept as a hi and a lo image in LDS (68 KB);
-//   * the slice of W (split once per weight version by ppt_text_lin_retile_split, x 2^b_pow2, fragment order, hi KiB then lo KiB)
-//     streams through a register ring; a wave owns SLN / 8 columns; three MFMAs per fragment pair, fp32 accumulation;
-//   * epilogue: x 2^-(a_pow2 + b_pow2) (+ bias) (+ residual) -> fp32 C[M, N], or the K chunk's partial product parts[c][M][N].
+//   * the block's rows of A (columns [512 c, 512 c + 512)) are staged ONCE into LDS: split16 multiplies them by 2^a_pow2, saturates
+//     to half's range (counted) and keeps a hi and a lo image (68 KB); the 16-bit forms copy them into a single image (34 KB);
+//   * the slice of W (re-tiled once per weight version by ppt_text_lin_retile_split / ppt_text_lin_retile16, fragment order; split16:
+//     x 2^b_pow2, hi KiB then lo KiB) streams through a register ring; a wave owns SLN / 8 columns; fp32 accumulation;
+//   * epilogue: (split16: x 2^-(a_pow2 + b_pow2)) (+ bias) (+ residual) -> fp32 C[M, N] or (16-bit forms) a 16-bit C rounded as
+//     ppt_gemm rounds (h16<T>::pack2: beyond the format's range is +-inf), or the K chunk's fp32 partial product parts[c][M][N].
 // SLN = 256 for N >= 1024 (in_proj: 26 x 6 = 156 workgroups), 128 below (N = 512: 26 x 4 (x 3 chunks) = 104 / 312 workgroups).
 #include "ppt_common.h"
 #include "gemm_common.h"
@@ -22,10 +25,34 @@ typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 constexpr int KC = 512;                                            // K chunk
 constexpr int RB = 2, R = 16 * RB;
 constexpr int AP = 2 * KC + 32;                                    // LDS pitch (bytes): = 32 mod 256
-constexpr int A_BYTES = R * AP;                                    // ONE image (hi or lo)
-constexpr int LDS_BYTES = 2 * A_BYTES;
+constexpr int A_BYTES = R * AP;                                    // ONE image (hi or lo, or the 16-bit one)
 constexpr int K1 = KC / 32;                                        // k-steps (16)
-constexpr int D1 = 4;                                              // ring depth in k-steps
+
+// what both public entry points hand the kernel
+struct LinArgs {
+    const void *A; int64_t lda;                                    // FORM's operand type (split16: fp32) [M, K]
+    const void *W;
+    const float *bias;
+    const float *residual; int64_t ld_res;
+    void *C; int64_t ldc;                                          // fp32, or (c16) FORM's 16-bit type
+    int M, N, K;
+    int c16;
+    int split_a_pow2, split_b_pow2; unsigned int *split_overflow;
+    int wave_prio;
+};
+
+template <int FORM> struct LinForm {                               // the 16-bit forms: one image, one MFMA per fragment
+    using T = typename std::conditional<FORM == PPT_BF16, bf16_t, f16_t>::type;
+    static constexpr bool SPLIT = false;
+    static constexpr int PARTS = 1;                                // KiB of W fragment per (16 columns x 32 k)
+    static constexpr int D1 = 8;                                   // ring depth in k-steps (the split form's bytes in flight)
+};
+template <> struct LinForm<PPT_F32> {
+    using T = f16_t;
+    static constexpr bool SPLIT = true;
+    static constexpr int PARTS = 2;
+    static constexpr int D1 = 4;
+};
 
 __device__ __forceinline__ void lds_barrier_l2()
 {
@@ -50,11 +77,13 @@ __device__ __forceinline__ void split4_l(const float (&x)[4], uint2 &H, uint2 &L
 }
 
 // NH = column halves of 16 a wave owns: 2 (SLN = 256) or 1 (SLN = 128)
-template <int NH>
-__global__ __launch_bounds__(512, 2) void text_lin_split_kernel(const ppt_text_lin_params p)
+template <int NH, int FORM>
+__global__ __launch_bounds__(512, 2) void text_lin_kernel(const LinArgs p)
 {
-    constexpr int SLN = 128 * NH;
-    constexpr int WAVE_SLICE = K1 * NH * 2048;                     // bytes of one wave's fragments per (slice, K chunk): hi + lo
+    using F = LinForm<FORM>;
+    using T = typename F::T;
+    constexpr int SLN = 128 * NH, NP = F::PARTS * NH, D1 = F::D1;
+    constexpr int WAVE_SLICE = K1 * NP * 1024;                     // bytes of one wave's fragments per (slice, K chunk)
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned char *ai = smem;
     const int lane = threadIdx.x & 63;
@@ -65,22 +94,35 @@ __global__ __launch_bounds__(512, 2) void text_lin_split_kernel(const ppt_text_l
     const int sc = blockIdx.x % (nsl * nck), s = sc % nsl, c = sc / nsl;          // ids that agree modulo (slices x chunks) share a weight slice
     const int row0 = (blockIdx.x / (nsl * nck)) * R;
     const int nrow = min(R, p.M - row0);
-    const float sa = pow2f(p.split_a_pow2), inv = pow2f(-(p.split_a_pow2 + p.split_b_pow2));
     uint32_t over = 0;
 
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.W), 0, (int)((size_t)p.N * p.K * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.W), 0, (int)((size_t)p.N * p.K * 2 * F::PARTS), 0x00020000);
     int o1 = ((c * nsl + s) * 8 + w) * WAVE_SLICE;
-    auto next1 = [&](uint4 (&f)[2 * NH]) {
+    auto next1 = [&](uint4 (&f)[NP]) {
 #pragma unroll
-        for (int i = 0; i < 2 * NH; ++i) f[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r1, lo16 + 1024 * i, o1, 0));
-        o1 += 2048 * NH;
+        for (int i = 0; i < NP; ++i) f[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r1, lo16 + 1024 * i, o1, 0));
+        o1 += 1024 * NP;
     };
-    uint4 g1[D1][2 * NH];
+    // 16-bit forms: the block's rows of A (this K chunk) are requested BEFORE the weight ring, so that waiting for them does not
+    // wait for the ring as well (loads return in order); rows past M: zeros
+    constexpr int PIECES16 = R * (KC / 8);
+    uint4 v16[F::SPLIT ? 1 : PIECES16 / 512];
+    if constexpr (!F::SPLIT) {
+        const uint16_t *A = (const uint16_t *)p.A + (size_t)c * KC;
+#pragma unroll
+        for (int it = 0; it < PIECES16 / 512; ++it) {
+            const int i = threadIdx.x + 512 * it, lr = i / (KC / 8), c8 = i % (KC / 8);
+            v16[it] = make_uint4(0, 0, 0, 0);
+            if (lr < nrow) v16[it] = *reinterpret_cast<const uint4 *>(A + (size_t)(row0 + lr) * p.lda + 8 * c8);
+        }
+    }
+    uint4 g1[D1][NP];
 #pragma unroll
     for (int i = 0; i < D1; ++i) next1(g1[i]);
 
-    // ---- the block's rows of A (fp32, this K chunk) -> scaled, saturated, split -> the hi and lo images (rows past M: zeros)
-    {
+    if constexpr (F::SPLIT) {
+        // ---- the block's rows of A (fp32, this K chunk) -> scaled, saturated, split -> the hi and lo images (rows past M: zeros)
+        const float sa = pow2f(p.split_a_pow2);
         const float *A = (const float *)p.A + (size_t)c * KC;
         constexpr int PIECES = R * (KC / 4);
         float4 v[PIECES / 512];
@@ -99,6 +141,13 @@ __global__ __launch_bounds__(512, 2) void text_lin_split_kernel(const ppt_text_l
             split4_l(x, H, L);
             *reinterpret_cast<uint2 *>(ai + lr * AP + 8 * c4) = H;
             *reinterpret_cast<uint2 *>(ai + A_BYTES + lr * AP + 8 * c4) = L;
+        }
+    } else {
+        // ---- ... and copied into the one image as they are
+#pragma unroll
+        for (int it = 0; it < PIECES16 / 512; ++it) {
+            const int i = threadIdx.x + 512 * it, lr = i / (KC / 8), c8 = i % (KC / 8);
+            *reinterpret_cast<uint4 *>(ai + lr * AP + 16 * c8) = v16[it];
         }
     }
     // bias and residual of this lane's output columns: requested now
@@ -126,7 +175,7 @@ __global__ __launch_bounds__(512, 2) void text_lin_split_kernel(const ppt_text_l
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
             fh[0][rb] = *reinterpret_cast<const uint4 *>(ha + rb * 16 * AP);
-            fl[0][rb] = *reinterpret_cast<const uint4 *>(ha + A_BYTES + rb * 16 * AP);
+            if constexpr (F::SPLIT) fl[0][rb] = *reinterpret_cast<const uint4 *>(ha + A_BYTES + rb * 16 * AP);
         }
 #pragma unroll
         for (int ks = 0; ks < K1; ++ks) {
@@ -134,17 +183,22 @@ __global__ __launch_bounds__(512, 2) void text_lin_split_kernel(const ppt_text_l
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb) {
                     fh[(ks + 1) & 1][rb] = *reinterpret_cast<const uint4 *>(ha + rb * 16 * AP + 64 * (ks + 1));
-                    fl[(ks + 1) & 1][rb] = *reinterpret_cast<const uint4 *>(ha + A_BYTES + rb * 16 * AP + 64 * (ks + 1));
+                    if constexpr (F::SPLIT) fl[(ks + 1) & 1][rb] = *reinterpret_cast<const uint4 *>(ha + A_BYTES + rb * 16 * AP + 64 * (ks + 1));
                 }
             }
 #pragma unroll
             for (int h = 0; h < NH; ++h) {
-                const uint4 wh = g1[ks % D1][2 * h], wl = g1[ks % D1][2 * h + 1];
+                if constexpr (F::SPLIT) {
+                    const uint4 wh = g1[ks % D1][2 * h], wl = g1[ks % D1][2 * h + 1];
 #pragma unroll
-                for (int rb = 0; rb < RB; ++rb) {
-                    a1[rb][h] = h16<f16_t>::mfma16(wh, fl[ks & 1][rb], a1[rb][h]);
-                    a1[rb][h] = h16<f16_t>::mfma16(wl, fh[ks & 1][rb], a1[rb][h]);
-                    a1[rb][h] = h16<f16_t>::mfma16(wh, fh[ks & 1][rb], a1[rb][h]);
+                    for (int rb = 0; rb < RB; ++rb) {
+                        a1[rb][h] = h16<f16_t>::mfma16(wh, fl[ks & 1][rb], a1[rb][h]);
+                        a1[rb][h] = h16<f16_t>::mfma16(wl, fh[ks & 1][rb], a1[rb][h]);
+                        a1[rb][h] = h16<f16_t>::mfma16(wh, fh[ks & 1][rb], a1[rb][h]);
+                    }
+                } else {
+#pragma unroll
+                    for (int rb = 0; rb < RB; ++rb) a1[rb][h] = h16<T>::mfma16(g1[ks % D1][h], fh[ks & 1][rb], a1[rb][h]);
                 }
             }
             if (ks + D1 < K1) next1(g1[ks % D1]);
@@ -152,19 +206,30 @@ __global__ __launch_bounds__(512, 2) void text_lin_split_kernel(const ppt_text_l
         }
     }
     // ---- epilogue: a lane holds four consecutive output columns of a row
-    float *C = p.C + (size_t)c * p.M * p.ldc;                        // (K chunks > 1: parts[c][M][N], ldc == N)
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
         const int lr = 16 * rb + l15;
         if (lr < nrow) {
 #pragma unroll
-            for (int h = 0; h < NH; ++h)
-                *reinterpret_cast<float4 *>(C + (size_t)(row0 + lr) * p.ldc + ncol + 16 * h) =
-                    make_float4(a1[rb][h][0] * inv + bv[h].x + rv[rb][h].x, a1[rb][h][1] * inv + bv[h].y + rv[rb][h].y,
-                                a1[rb][h][2] * inv + bv[h].z + rv[rb][h].z, a1[rb][h][3] * inv + bv[h].w + rv[rb][h].w);
+            for (int h = 0; h < NH; ++h) {
+                if constexpr (F::SPLIT) {
+                    const float inv = pow2f(-(p.split_a_pow2 + p.split_b_pow2));
+                    float *C = (float *)p.C + (size_t)c * p.M * p.ldc;              // (K chunks > 1: parts[c][M][N], ldc == N)
+                    *reinterpret_cast<float4 *>(C + (size_t)(row0 + lr) * p.ldc + ncol + 16 * h) =
+                        make_float4(a1[rb][h][0] * inv + bv[h].x + rv[rb][h].x, a1[rb][h][1] * inv + bv[h].y + rv[rb][h].y,
+                                    a1[rb][h][2] * inv + bv[h].z + rv[rb][h].z, a1[rb][h][3] * inv + bv[h].w + rv[rb][h].w);
+                } else {
+                    // ((acc + bias) + residual): ppt_gemm's epilogue order
+                    const float4 v = make_float4(a1[rb][h][0] + bv[h].x + rv[rb][h].x, a1[rb][h][1] + bv[h].y + rv[rb][h].y,
+                                                 a1[rb][h][2] + bv[h].z + rv[rb][h].z, a1[rb][h][3] + bv[h].w + rv[rb][h].w);
+                    const size_t off = (size_t)c * p.M * p.ldc + (size_t)(row0 + lr) * p.ldc + ncol + 16 * h;
+                    if (p.c16) *reinterpret_cast<uint2 *>((uint16_t *)p.C + off) = make_uint2(h16<T>::pack2(v.x, v.y), h16<T>::pack2(v.z, v.w));
+                    else *reinterpret_cast<float4 *>((float *)p.C + off) = v;
+                }
+            }
         }
     }
-    split_report(over, p.split_overflow);
+    if constexpr (F::SPLIT) split_report(over, p.split_overflow);
 }
 
 // fragment order: Wt[c][s][w][ks < 16][h < NH][hi, lo][lane][8] <- W[SLN s + 16 NH w + 16 h + l15][512 c + 32 ks + 8 kg ..) * 2^b_pow2      W [N, K] f32
@@ -192,7 +257,42 @@ __global__ __launch_bounds__(256) void text_lin_retile_split_kernel(const float 
     *reinterpret_cast<uint4 *>(dst + 1024) = make_uint4(l0.x, l0.y, l1.x, l1.y);
 }
 
+// the 16-bit forms' order: Wt[c][s][w][ks < 16][h < NH][lane][8] <- W[SLN s + 16 NH w + 16 h + l15][512 c + 32 ks + 8 kg ..)   W [N, K] 16-bit
+template <int NH>
+__global__ __launch_bounds__(256) void text_lin_retile16_kernel(const uint16_t *__restrict__ W, unsigned char *__restrict__ Wt, int N, int K)
+{
+    constexpr int SLN = 128 * NH;
+    const int nsl = N / SLN, nck = K / KC;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nck * nsl * 8 * K1 * NH * 64) return;
+    const int lane = i & 63, f = (i >> 6) % (K1 * NH), w = (i / (64 * K1 * NH)) & 7, sc = i / (64 * K1 * NH * 8);
+    const int s = sc % nsl, c = sc / nsl, ks = f / NH, h = f % NH;
+    const int l15 = lane & 15, kg = lane >> 4;
+    const uint16_t *src = W + (size_t)(SLN * s + 16 * NH * w + 16 * h + l15) * K + KC * c + 32 * ks + 8 * kg;
+    *reinterpret_cast<uint4 *>(Wt + (size_t)i * 16) = *reinterpret_cast<const uint4 *>(src);
+}
+
 __host__ int slice_halves(int N) { return N >= 1024 ? 2 : 1; }
+
+template <int NH, int FORM>
+void launch(const LinArgs &p, hipStream_t st)
+{
+    constexpr int LDS_BYTES = LinForm<FORM>::PARTS * A_BYTES;
+    static const int attrs_once = [] {
+        (void)hipFuncSetAttribute((const void *)text_lin_kernel<NH, FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        return 0;
+    }();
+    (void)attrs_once;
+    const int grid = (p.N / (128 * NH)) * (p.K / KC) * ((p.M + R - 1) / R);
+    hipLaunchKernelGGL((text_lin_kernel<NH, FORM>), dim3(grid), dim3(512), LDS_BYTES, st, p);
+}
+
+template <int FORM>
+void launch_form(const LinArgs &p, hipStream_t st)
+{
+    if (slice_halves(p.N) == 2) launch<2, FORM>(p, st);
+    else launch<1, FORM>(p, st);
+}
 
 }  // namespace
 
@@ -212,25 +312,50 @@ extern "C" int ppt_text_lin_retile_split(const float *W, void *Wt, int N, int K,
 extern "C" int ppt_text_lin_split(const ppt_text_lin_params *pp, void *stream)
 {
     if (!pp) return PPT_EINVAL;
-    ppt_text_lin_params p = *pp;
-    if (!p.A || !p.W || !p.C || p.M <= 0 || p.N <= 0 || p.K <= 0) return PPT_EINVAL;
-    if (p.K % KC || p.N % 256) return PPT_EUNSUPPORTED;
-    if (p.lda < p.K || (p.lda % 4) || p.ldc < p.N || (p.ldc % 4) || abs(p.split_a_pow2) > 24 || abs(p.split_b_pow2) > 24) return PPT_EINVAL;
-    if (((uintptr_t)p.A | (uintptr_t)p.W | (uintptr_t)p.C | (uintptr_t)p.bias | (uintptr_t)p.residual) & 15) return PPT_EINVAL;
-    if (p.residual && (p.ld_res < p.N || (p.ld_res % 4))) return PPT_EINVAL;
-    if (p.K > KC && (p.bias || p.residual || p.ldc != p.N)) return PPT_EINVAL;          // K chunks leave as plain partial products
-    if (p.wave_prio == 0) p.wave_prio = ppt_get_wave_priority();
-    static const int attrs_once = [] {
-        (void)hipFuncSetAttribute((const void *)text_lin_split_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute((const void *)text_lin_split_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        return 0;
-    }();
-    (void)attrs_once;
-    const int nh = slice_halves(p.N);
-    const int grid = (p.N / (128 * nh)) * (p.K / KC) * ((p.M + R - 1) / R);
-    hipStream_t st = ppt_stream(stream);
-    if (nh == 2) hipLaunchKernelGGL((text_lin_split_kernel<2>), dim3(grid), dim3(512), LDS_BYTES, st, p);
-    else hipLaunchKernelGGL((text_lin_split_kernel<1>), dim3(grid), dim3(512), LDS_BYTES, st, p);
+    const ppt_text_lin_params &q = *pp;
+    if (!q.A || !q.W || !q.C || q.M <= 0 || q.N <= 0 || q.K <= 0) return PPT_EINVAL;
+    if (q.K % KC || q.N % 256) return PPT_EUNSUPPORTED;
+    if (q.lda < q.K || (q.lda % 4) || q.ldc < q.N || (q.ldc % 4) || abs(q.split_a_pow2) > 24 || abs(q.split_b_pow2) > 24) return PPT_EINVAL;
+    if (((uintptr_t)q.A | (uintptr_t)q.W | (uintptr_t)q.C | (uintptr_t)q.bias | (uintptr_t)q.residual) & 15) return PPT_EINVAL;
+    if (q.residual && (q.ld_res < q.N || (q.ld_res % 4))) return PPT_EINVAL;
+    if (q.K > KC && (q.bias || q.residual || q.ldc != q.N)) return PPT_EINVAL;          // K chunks leave as plain partial products
+    const LinArgs p = {q.A, q.lda, q.W, q.bias, q.residual, q.ld_res, q.C, q.ldc, q.M, q.N, q.K, 0,
+                       q.split_a_pow2, q.split_b_pow2, q.split_overflow, q.wave_prio ? q.wave_prio : ppt_get_wave_priority()};
+    launch_form<PPT_F32>(p, ppt_stream(stream));
+    PPT_CHECK_LAUNCH();
+    return PPT_OK;
+}
+
+extern "C" int ppt_text_lin_retile16(const void *W, void *Wt, int N, int K, void *stream)
+{
+    if (!W || !Wt || (((uintptr_t)W | (uintptr_t)Wt) & 15)) return PPT_EINVAL;
+    if (N <= 0 || K <= 0 || K % KC || N % 256) return PPT_EUNSUPPORTED;
+    const int pieces = N * (K / 8);
+    if (slice_halves(N) == 2)
+        hipLaunchKernelGGL(text_lin_retile16_kernel<2>, dim3((pieces + 255) / 256), dim3(256), 0, ppt_stream(stream), (const uint16_t *)W, (unsigned char *)Wt, N, K);
+    else
+        hipLaunchKernelGGL(text_lin_retile16_kernel<1>, dim3((pieces + 255) / 256), dim3(256), 0, ppt_stream(stream), (const uint16_t *)W, (unsigned char *)Wt, N, K);
+    PPT_CHECK_LAUNCH();
+    return PPT_OK;
+}
+
+extern "C" int ppt_text_lin16(const ppt_text_lin16_params *pp, void *stream)
+{
+    if (!pp) return PPT_EINVAL;
+    const ppt_text_lin16_params &q = *pp;
+    if (!q.A || !q.W || !q.C || q.M <= 0 || q.N <= 0 || q.K <= 0) return PPT_EINVAL;
+    if (q.dtype != PPT_F16 && q.dtype != PPT_BF16) return PPT_EINVAL;
+    if (q.c_dtype != PPT_F32 && q.c_dtype != q.dtype) return PPT_EINVAL;
+    if (q.K % KC || q.N % 256) return PPT_EUNSUPPORTED;
+    if (q.lda < q.K || (q.lda % 8) || q.ldc < q.N || (q.ldc % 4)) return PPT_EINVAL;
+    if (((uintptr_t)q.A | (uintptr_t)q.W | (uintptr_t)q.bias | (uintptr_t)q.residual) & 15) return PPT_EINVAL;
+    if (((uintptr_t)q.C) & (q.c_dtype == PPT_F32 ? 15 : 7)) return PPT_EINVAL;
+    if (q.residual && (q.ld_res < q.N || (q.ld_res % 4))) return PPT_EINVAL;
+    if (q.K > KC && (q.bias || q.residual || q.ldc != q.N || q.c_dtype != PPT_F32)) return PPT_EINVAL;   // K chunks: fp32 partial products
+    const LinArgs p = {q.A, q.lda, q.W, q.bias, q.residual, q.ld_res, q.C, q.ldc, q.M, q.N, q.K, q.c_dtype != PPT_F32,
+                       0, 0, nullptr, q.wave_prio ? q.wave_prio : ppt_get_wave_priority()};
+    if (q.dtype == PPT_F16) launch_form<PPT_F16>(p, ppt_stream(stream));
+    else launch_form<PPT_BF16>(p, ppt_stream(stream));
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }

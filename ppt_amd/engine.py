@@ -881,22 +881,34 @@ TEXT_MLP_PAIR_LAST = os.environ.get("PPT_TEXT_MLP_PAIR_LAST", "1") != "0"  # the
 TEXT_MLP_PAIR_SPLIT = os.environ.get("PPT_TEXT_MLP_PAIR_SPLIT", "1") != "0"
 
 
-# The attention half's four linears of a text layer in that mode on csrc/text_lin_split.hip (rows stationary, weight halves streamed):
-# in_proj, out_proj (+ bias + residual), and their input-gradient products.  0: the split16 tile GEMMs.
+# The attention half's four linears of a text layer on csrc/text_lin_split.hip (rows stationary, weight streamed): in_proj, out_proj
+# (+ bias + residual), and their input-gradient products -- in the split16 form (fp32 operands as hi + lo half pairs) and, where the
+# split-K hand-over runs, in the 16-bit form of the mixed mode.  Supported switch: 0 restores the tile GEMMs.
 TEXT_LIN_SPLIT = os.environ.get("PPT_TEXT_LIN_SPLIT", "1") != "0"
 
 
 def _text_lin_ok(Ta, width):
-    return Ta == torch.float32 and TEXT_LIN_SPLIT and ops.split16_enabled() and width == 512
+    return TEXT_LIN_SPLIT and width == 512 and (Ta in ops.HALF or (Ta == torch.float32 and ops.split16_enabled()))
 
 
 def _text_lin_tiles(sd, name, wca, transposed=False):
-    """The hi + lo half copy of weight `name` ([N, K]; transposed: of its transpose, the dX operand) for ops.text_lin_split, made with
-    the B pre-scale in force (a new fit re-makes it)."""
+    """The fragment-ordered copy of weight `name` ([N, K]; transposed: of its transpose, the dX operand) for the text-lin kernel:
+    16-bit, the operand the WeightCache keeps; split16, the hi + lo half copy made with the B pre-scale in force (a new fit re-makes
+    it)."""
     w = sd[name]
+    if wca.dtype in ops.HALF:
+        return wca.derived(("text_lin16", name, transposed), (w,),
+                           lambda: ops.text_lin_retile16(wca.get(w, "wt") if transposed else wca.get(w)))
     b = ops.SPLIT16_POW2[1]
     return wca.derived(("text_lin_split", name, transposed, b), (w,),
                        lambda: ops.text_lin_retile_split(wca.get(w, "wt") if transposed else wca.get(w), b))
+
+
+def _text_lin(a, sd, name, wca, transposed=False, **kw):
+    """a @ W^T (+ bias) (+ residual) of the attention half on the text-lin kernel of wca's operand form (see _text_lin_tiles):
+    16-bit in -> 16-bit out unless out= is fp32; split16 fp32 in -> fp32 out; K > 512: the fp32 partial products."""
+    wt = _text_lin_tiles(sd, name, wca, transposed)
+    return ops.text_lin16(a, wt, **kw) if wca.dtype in ops.HALF else ops.text_lin_split(a, wt, **kw)
 
 
 def _text_mlp_pair_ok(Tm):
@@ -984,7 +996,7 @@ def text_tower_forward(sd, wc, prompts, eot_pos, heads, layers, save, eff_len=No
     # the residual and the bias -- by the LayerNorm that reads the result anyway (ops.layernorm_fwd_sum): no reduction launch.
     # (16-bit modes and split16; the fp32 parity mode keeps the single-launch summation order)
     splitk = TEXT_SPLITK and (T in ops.HALF or ops.split16_enabled()) and Tm == T and not fuse and M <= 4096 and Wd == 512
-    lin_split = _text_lin_ok(Ta, Wd) and not fuse
+    lin_split = _text_lin_ok(Ta, Wd) and not fuse and (Ta == torch.float32 or splitk)
     pending = None                  # (x_mid, c_proj bias, partial products) of the previous layer: its output is formed by this layer's LN1
     for i in range(layers):
         p = f"transformer.resblocks.{i}."
@@ -994,7 +1006,7 @@ def text_tower_forward(sd, wc, prompts, eot_pos, heads, layers, save, eff_len=No
                                                     write_xs=x, save_stats=save)
             pending = None
             if lin_split:
-                qkv = ops.text_lin_split(h, _text_lin_tiles(sd, p + "attn.in_proj_weight", wca), bias=sd[p + "attn.in_proj_bias"])
+                qkv = _text_lin(h, sd, p + "attn.in_proj_weight", wca, bias=sd[p + "attn.in_proj_bias"])
             else:
                 qkv = ops.gemm(h, wca.get(sd[p + "attn.in_proj_weight"]), out_dtype=Ta, bias=sd[p + "attn.in_proj_bias"])
         elif fuse and add is None:
@@ -1009,7 +1021,7 @@ def text_tower_forward(sd, wc, prompts, eot_pos, heads, layers, save, eff_len=No
                                                 add_rows=add_rows, write_xs=x if add is not None else None,
                                                 save_stats=save)
             if lin_split:
-                qkv = ops.text_lin_split(h, _text_lin_tiles(sd, p + "attn.in_proj_weight", wca), bias=sd[p + "attn.in_proj_bias"])
+                qkv = _text_lin(h, sd, p + "attn.in_proj_weight", wca, bias=sd[p + "attn.in_proj_bias"])
             else:
                 qkv = ops.gemm(h, wca.get(sd[p + "attn.in_proj_weight"]), out_dtype=Ta, bias=sd[p + "attn.in_proj_bias"])
         add, add_rows = None, 0
@@ -1019,7 +1031,7 @@ def text_tower_forward(sd, wc, prompts, eot_pos, heads, layers, save, eff_len=No
             a, lse = ops.attention_fwd(qkv, C, L, heads, ATTN_SCALE, True, want_lse=save)
         x_mid = torch.empty_like(x)
         if lin_split:
-            ops.text_lin_split(a, _text_lin_tiles(sd, p + "attn.out_proj.weight", wca), bias=sd[p + "attn.out_proj.bias"], residual=x, out=x_mid)
+            _text_lin(a, sd, p + "attn.out_proj.weight", wca, bias=sd[p + "attn.out_proj.bias"], residual=x, out=x_mid)
         else:
             ops.gemm(a, wca.get(sd[p + "attn.out_proj.weight"]), out=x_mid, bias=sd[p + "attn.out_proj.bias"], residual=x)
         pre = torch.empty((M, sd[p + "mlp.c_fc.weight"].shape[0]), dtype=Tm, device=dev) if save else None
@@ -1149,7 +1161,7 @@ def text_tower_backward(sd, wc, s, dout, grad_scale=1.0):
             _, _, _, g_t = ops.layernorm_bwd(d_h2, ly["x_mid"], sd[p + "ln_2.weight"], ly["mean2"], ly["rstd2"], dx=g,
                                              accumulate=True, copy_dtype=Ta)
         if lin_split:
-            d_a = ops.text_lin_split(g_t, _text_lin_tiles(sd, p + "attn.out_proj.weight", wca, True))
+            d_a = _text_lin(g_t, sd, p + "attn.out_proj.weight", wca, True)
         else:
             d_a = ops.gemm(g_t, wca.get(sd[p + "attn.out_proj.weight"], "wt"), out_dtype=Ta)
         if P:
@@ -1157,7 +1169,7 @@ def text_tower_backward(sd, wc, s, dout, grad_scale=1.0):
         else:
             d_qkv = ops.attention_bwd(ly["qkv"], ly["a"], d_a, ly["lse"], C, L, heads, ATTN_SCALE, True)
         if splitk:                  # K = 1536: three slices
-            dparts = (ops.text_lin_split(d_qkv, _text_lin_tiles(sd, p + "attn.in_proj_weight", wca, True)) if lin_split
+            dparts = (_text_lin(d_qkv, sd, p + "attn.in_proj_weight", wca, True) if lin_split
                       else ops.gemm_splitk(d_qkv, wca.get(sd[p + "attn.in_proj_weight"], "wt"), 3))
             _, g_t = ops.layernorm_bwd_sum(dparts, ly["x"],
                                            sd[p + "ln_1.weight"], ly["mean1"], ly["rstd1"], g, accumulate=True, copy_dtype=Tm)

@@ -512,6 +512,47 @@ def text_lin_split(a, wt, *, bias=None, residual=None, out=None, a_pow2=None):
     return out
 
 
+def text_lin_retile16(w):
+    """w [N, K] 16-bit row-major (N a multiple of 256, K of 512) -> the fragment-ordered copy text_lin16 reads (uint8, N * K * 2
+    bytes, the same values); remembers (N, K, dtype)."""
+    assert w.dtype in HALF and w.dim() == 2
+    _chk(w, w.dtype, "w")
+    N, K = w.shape
+    wt = torch.empty((N * K * 2,), dtype=torch.uint8, device=w.device)
+    _lib.check(_lib.lib().ppt_text_lin_retile16(_p(w), _p(wt), N, K, _stream()), "ppt_text_lin_retile16")
+    wt.ppt_shape, wt.ppt_dtype = (N, K), w.dtype
+    return wt
+
+
+def text_lin16(a, wt, *, bias=None, residual=None, out=None, out_dtype=None):
+    """a [M, K] 16-bit @ W^T (+ bias) (+ residual), rows stationary (csrc/text_lin_split.hip; wt = text_lin_retile16(W), W in a's
+    dtype) -> out [M, N] in out_dtype (a's dtype by default, or fp32; out= may be a strided view); K > 512: the K / 512 fp32 partial
+    products [K / 512, M, N] (no bias / residual).  16-bit results are rounded as gemm rounds them."""
+    N, K = wt.ppt_shape
+    M = a.shape[0]
+    assert a.dtype == wt.ppt_dtype and a.dim() == 2 and a.shape[1] == K and a.stride(1) == 1
+    kc = K // 512
+    if kc > 1:
+        assert bias is None and residual is None and out is None and out_dtype in (None, torch.float32)
+        out = torch.empty((kc, M, N), dtype=torch.float32, device=a.device)
+    elif out is None:
+        out = torch.empty((M, N), dtype=out_dtype or a.dtype, device=a.device)
+    assert out.dtype in (torch.float32, a.dtype) and out.stride(-1) == 1
+    p = _lib.TextLin16Params()
+    p.A, p.lda, p.W, p.bias = _p(a), a.stride(0), _p(wt), _p(bias)
+    if residual is not None:
+        assert residual.dtype == torch.float32 and residual.stride(-1) == 1
+        p.residual, p.ld_res = _p(residual), residual.stride(-2)
+    p.C, p.ldc = _p(out), (N if kc > 1 else out.stride(0))
+    p.M, p.N, p.K, p.dtype, p.c_dtype = M, N, K, _DT[a.dtype], _DT[out.dtype]
+    if profiler is not None:
+        profiler.begin("gemm_bf16", 2.0 * M * N * K, "ppt_text_lin16")
+    _lib.check(_lib.lib().ppt_text_lin16(ctypes.byref(p), _stream()), "ppt_text_lin16")
+    if profiler is not None:
+        profiler.end()
+    return out
+
+
 def text_mlp_pair(a, w1t, w2t, *, bias=None, pre=None, backward=False, ln=None, ln_eps=1e-5, save_stats=False):
     """The MLP half of a CLIP text layer in one launch (csrc/text_mlp.hip) -> the eight slices' partial products [8, M, 512] f32.
     forward: QuickGELU(a w1^T + bias) w2^T, `pre` (optional, [M, 2048] 16-bit) receives the pre-activation; backward=True:
