@@ -47,7 +47,7 @@ const char *ppt_strerror(int code);
  *    ppt_text_mlp_retile (new: csrc/text_mlp.hip), ppt_lnlin / ppt_lnlin_retile (new: csrc/lnlin.hip),
  *    ppt_text_mlp_retile_split + the split16 fields of ppt_text_mlp_params (csrc/text_mlp_split.hip), ppt_text_lin_split /
  *    ppt_text_lin_retile_split (csrc/text_lin_split.hip); later, additive only (no existing signature or struct changed):
- *    ppt_text_lin16 / ppt_text_lin_retile16 (the 16-bit form of ppt_text_lin_split).
+ *    ppt_text_lin16 / ppt_text_lin_retile16 (the 16-bit form of ppt_text_lin_split); ppt_cloud_prep_f32 / ppt_cloud_draws (csrc/cloud_prep.hip).
  * 6: ppt_gemm_params.split16 / split_a_pow2 / split_b_pow2 (new trailing fields: fp32 operands as hi + lo half pairs),
  *    ppt_attention_fwd_split16 / ppt_attention_bwd_split16 (new), ppt_pointmlp_cloud_rstd / ppt_pointmlp_pq (new).
  * 5: ppt_labels_check (new), ppt_gemm256 (new: the 256-row macro-tile GEMM core), ppt_set_gemm256 / ppt_get_gemm256 (new),
@@ -733,6 +733,33 @@ int ppt_transpose(const void *src, int src_dtype, void *dst, int dst_dtype, int 
 int ppt_col_sums(const void *x, int x_dtype, int M, int D, int64_t ldx, float *partial, void *stream);
 /* sum the [P, D] partial buffers produced by col_sum / dw_partial style outputs -> [D] */
 int ppt_reduce_rows(const float *partial, int P, int D, float *out, int accumulate, void *stream);
+
+/* ---- device-resident input pipeline (ppt_amd/data/device_loader.py) --------------------------------------------------------
+ * What the reference's datasets do to a sample after the row selection -- data/dataset_3d.py:33-38 pc_normalize, :155-160
+ * translate_pointcloud, np.random.shuffle, the row gathers of ModelNet (:294-296), ScanObjectNN (:407) and ShapeNetPart
+ * (:752-755) -- for a batch of B clouds taken from a set that is resident on the device.  One workgroup per output cloud.
+ *   src [M, Nmax, C] f32 (C >= 3, xyz = the first three columns), lengths [M] i32 or NULL (= Nmax), item [B] i64 in [0, M),
+ *   sel [B, n] i64 rows of cloud item[b] (NULL: rows 0 .. n-1)  ->  p[i] = src[item[b], sel[b, i], 0:3];
+ *   normalize: c = sequential f32 sum over i = 0 .. n-1, / n;  q = p - c;  m = max_i sqrt((x*x + y*y) + z*z);  q / m;
+ *   translate: (float)((double)v * scale[b, axis] + shift[b, axis]), scale / shift [B, 3] f64, two roundings in f64, one to f32;
+ *   perm [B, n] i32 or NULL: out[b, i] = x[perm[b, i]];
+ *   seg_src [M, Nmax] i32 -> seg_out [B, n] i64 through the same sel and perm (both NULL or both given);
+ *   out [B, n, 3] f32, 16-byte aligned.   n <= 8192, Nmax <= 16384.
+ * Every rounding is the reference's (numpy's), so the output is bit-identical given the same draws.  An index outside its range
+ * (item, sel, perm, a length above Nmax) is clamped into it: it selects a wrong row, never memory outside the arrays. */
+int ppt_cloud_prep_f32(const float *src, int M, int Nmax, int C, const int32_t *lengths, const int64_t *item, int B,
+                       const int64_t *sel, int n, int normalize, int translate, const double *scale, const double *shift,
+                       const int32_t *perm, const int32_t *seg_src, int64_t *seg_out, float *out, void *stream);
+/* The draws of that pipeline from Philox4x32-10 (counter = (index[b], epoch, slot, block), key = seed): a sample's draws depend
+ * on its index, the epoch and the seed only.  Every output is optional (NULL = not drawn):
+ *   start [B] i64 in [0, rows), sel [B, n] i64 in [0, rows) (rows = rows[b], or rows_all when rows == NULL; no modulo bias),
+ *   scale [B, 3] f64 in [2/3, 3/2) and shift [B, 3] f64 in [-0.2, 0.2) (53 random bits each; given together),
+ *   perm [B, n] i32: the order of n (32-bit key, position) pairs sorted in LDS, ties by position.   n <= 8192.
+ * raw_ctr [raw_count, 4] u32 -> raw_out [raw_count, 4] u32 (16-byte aligned): the generator's output words for explicit
+ * counters under the same key (known-answer checks); may be combined with, or given without, the batch arguments. */
+int ppt_cloud_draws(const int64_t *index, int B, const int32_t *rows, int rows_all, int n, uint64_t seed, uint32_t epoch,
+                    int64_t *start, double *scale, double *shift, int32_t *perm, int64_t *sel, const uint32_t *raw_ctr,
+                    int raw_count, uint32_t *raw_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # the scalar chain is bit-stable.  PPT_SLP=1 re-enables it for A/B timing.
 COMMON = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-inline-asm",
           "-fno-gpu-rdc"] + ([] if os.environ.get("PPT_SLP") == "1" else ["-fno-slp-vectorize"])
-PER_FILE = {"fps.hip": ["-ffp-contract=off"], "knn_group.hip": ["-ffp-contract=off"]}
+PER_FILE = {"fps.hip": ["-ffp-contract=off"], "knn_group.hip": ["-ffp-contract=off"],
+            # the input pipeline reproduces numpy bit for bit: no contraction, IEEE-rounded fp32 `/` and sqrtf (hipcc's default, pinned)
+            "cloud_prep.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]}
 
 
 def sources():

@@ -1,0 +1,297 @@
+"""A dataset that lives on the device and a loader that produces its batches there ("device-resident dataset").
+
+What the reference's datasets do per sample, every epoch, in DataLoader workers (data/dataset_3d.py):
+
+    ModelNet / ModelNet_fs (:291-326)   farthest point sampling N -> npoints from a fresh random start, pc_normalize, and for the
+                                        train split translate_pointcloud + np.random.shuffle
+    ScanObjectNN (:406-419)             the first num_points rows (no normalisation), and for the train split translate + shuffle
+    ShapeNetPart (:734-757)             pc_normalize, then np.random.choice(len, npoints, replace=True) rows of the cloud and of its
+                                        per-point part labels
+
+ModelNet40 at 8192 points is under 1 GB; the raw clouds simply stay in device memory (`DeviceCloudSet`).  `DeviceBatchLoader` then
+produces a batch with one batched launch of the path's FPS kernel (csrc/fps.hip) and one launch of csrc/cloud_prep.hip for
+everything after it -- no workers, no pickling, no host copy of a cloud -- `ahead` batches in front of the consumer on the grouping
+stream (graphs.shared_group_stream), each yielded tensor carrying its completion event like a DevicePrefetcher batch.
+
+The random draws come from one of two places:
+
+    draws="numpy"   the host draws from `np.random.RandomState([seed, epoch, rank])`, sample after sample in batch order, each sample
+                    in the reference's order (`numpy_draws`): randint(0, N) when the stored cloud has more rows than npoints, then
+                    for the train split uniform(2/3, 3/2, 3), uniform(-0.2, 0.2, 3), permutation(npoints); for part-seg
+                    choice(len, npoints, replace=True).  Given the same generator state a batch is bit-identical to what the
+                    reference's Dataset.__getitem__ returns (tests/test_datapipe_gpu.py against tests/golden/g_datapipe.npz).
+    draws="device"  csrc/cloud_prep.hip: ppt_cloud_draws, Philox4x32-10 keyed by `seed` with the counter (dataset index, epoch, draw,
+                    block): a sample's draws do not depend on the batch size, the number of ranks or the batch it lands in, and
+                    the launching thread does no per-sample work.
+"""
+import collections
+import math
+
+import numpy as np
+import torch
+
+RECIPES = ("modelnet", "scanobjectnn", "shapenetpart")
+MAX_ROWS = 16384          # csrc/fps.hip: N <= 16384
+MAX_NPOINTS = 8192        # csrc/cloud_prep.hip: one cloud of the batch in LDS
+
+
+def epoch_indices(n_items, epoch=0, shuffle=True, seed=0, drop_last=False, rank=0, world_size=1):
+    """The dataset indices rank `rank` visits in epoch `epoch`, in order: torch.utils.data.DistributedSampler's rule (permutation
+    from a torch.Generator seeded with seed + epoch, padding by wrap-around or truncation to a multiple of world_size,
+    then rank::world_size); world_size = 1 is the plain shuffled / sequential order."""
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} outside [0, {world_size})")
+    if drop_last and n_items % world_size != 0:
+        num = math.ceil((n_items - world_size) / world_size)
+    else:
+        num = math.ceil(n_items / world_size)
+    total = num * world_size
+    if shuffle:
+        g = torch.Generator()
+        g.manual_seed(int(seed) + int(epoch))
+        idx = torch.randperm(n_items, generator=g).tolist()
+    else:
+        idx = list(range(n_items))
+    if not drop_last:
+        pad = total - len(idx)
+        idx += idx[:pad] if pad <= len(idx) else (idx * math.ceil(pad / len(idx)))[:pad]
+    else:
+        idx = idx[:total]
+    return np.asarray(idx[rank:total:world_size], dtype=np.int64)
+
+
+def numpy_draws(rs, recipe, train, rows, npoints):
+    """One sample's draws from the np.random.RandomState `rs`, in the order the reference's __getitem__ makes them.  -> dict with
+    the ones this recipe / split needs of start (int), scale [3] f64, shift [3] f64, perm [npoints], sel [npoints]."""
+    d = {}
+    if recipe == "shapenetpart":
+        d["sel"] = rs.choice(rows, npoints, replace=True)                     # dataset_3d.py:752
+        return d
+    if recipe == "modelnet" and npoints < rows:
+        d["start"] = rs.randint(0, rows)                                      # :50, inside farthest_point_sample
+    if train:
+        d["scale"] = rs.uniform(low=2. / 3., high=3. / 2., size=[3])          # :156
+        d["shift"] = rs.uniform(low=-0.2, high=0.2, size=[3])                 # :157
+        d["perm"] = rs.permutation(npoints)                                   # np.random.shuffle(cloud): the same swaps, applied to arange
+    return d
+
+
+def _rows_of(a):
+    return [np.asarray(x) for x in a] if isinstance(a, (list, tuple)) else None
+
+
+class DeviceCloudSet:
+    """The raw clouds of a dataset, uploaded once.
+
+    points   [M, Nmax, C >= 3] float32 array / tensor, or a list of M arrays [N_i, C] (padded to the longest; `lengths` is then
+             derived).  xyz = the first three columns; further columns (normals) stay resident but no recipe reads them.
+    labels   [M] integer class labels.
+    seg      [M, Nmax] int32 per-point part labels (or a list of [N_i]) -- a part-segmentation set.  Its clouds are normalised ONCE
+             here, on the host, with ppt_amd.data.pc_normalize.  The reference (dataset_3d.py:750) re-normalises its cached array
+             on every access, so from the second epoch on it normalises an already normalised cloud and the values drift by
+             rounding; that is not reproduced -- every epoch sees the first access's values.
+    lengths  [M] valid rows per cloud (None: all Nmax).
+    Nmax <= 16384 (the FPS kernel's limit).  float32 only."""
+
+    def __init__(self, points, labels, seg=None, lengths=None, device=None):
+        from .dataset_3d import pc_normalize
+        ragged = _rows_of(points)
+        if ragged is not None:
+            for x in ragged:
+                self._check_dtype(x.dtype)
+            if lengths is not None:
+                raise ValueError("lengths is derived from a list of clouds; do not give both")
+            lengths = np.asarray([x.shape[0] for x in ragged], dtype=np.int32)
+            C = ragged[0].shape[1]
+            pts = np.zeros((len(ragged), int(lengths.max()), C), dtype=np.float32)
+            for i, x in enumerate(ragged):
+                pts[i, :x.shape[0]] = x
+            if seg is not None:
+                sg = np.zeros(pts.shape[:2], dtype=np.int32)
+                for i, s in enumerate(_rows_of(seg)):
+                    sg[i, :len(s)] = s
+                seg = sg
+        else:
+            pts = points.detach().cpu().numpy() if torch.is_tensor(points) else np.asarray(points)
+            self._check_dtype(pts.dtype)
+        if pts.ndim != 3 or pts.shape[2] < 3:
+            raise ValueError(f"points must be [M, Nmax, C >= 3], got {pts.shape}")
+        M, Nmax, _ = pts.shape
+        if Nmax > MAX_ROWS:
+            raise ValueError(f"DeviceCloudSet: clouds of at most {MAX_ROWS} rows (got {Nmax}): the FPS kernel's limit")
+        labels = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels).reshape(-1).astype(np.int64)
+        if labels.shape[0] != M:
+            raise ValueError(f"{labels.shape[0]} labels for {M} clouds")
+        if lengths is not None:
+            lengths = np.asarray(lengths).astype(np.int32).reshape(-1)
+            if lengths.shape[0] != M or lengths.min() < 1 or lengths.max() > Nmax:
+                raise ValueError("lengths must be [M] with 1 <= length <= Nmax")
+        if seg is not None:
+            seg = np.ascontiguousarray(np.asarray(seg.cpu() if torch.is_tensor(seg) else seg).astype(np.int32))
+            if seg.shape != (M, Nmax):
+                raise ValueError(f"seg must be {(M, Nmax)}, got {seg.shape}")
+            pts = np.array(pts, dtype=np.float32, copy=True)
+            for i in range(M):
+                L = Nmax if lengths is None else int(lengths[i])
+                pts[i, :L, 0:3] = pc_normalize(pts[i, :L, 0:3])
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.lengths_host = lengths                                            # numpy copy: the host-side draws need the row counts
+        self.points = torch.from_numpy(np.ascontiguousarray(pts)).to(self.device)
+        self.labels = torch.from_numpy(labels).to(self.device)
+        self.seg = None if seg is None else torch.from_numpy(seg).to(self.device)
+        self.lengths = None if lengths is None else torch.from_numpy(lengths).to(self.device)
+
+    @staticmethod
+    def _check_dtype(dt):
+        if dt != np.float32:
+            raise TypeError(f"DeviceCloudSet: float32 clouds only (got {dt}): the reference's datasets hold float32 arrays and a float64 "
+                            "array would be sampled and normalised in float64 arithmetic, which the fp32 kernels do not reproduce")
+
+    def __len__(self):
+        return self.points.shape[0]
+
+    def rows(self, idx):
+        """valid rows of the clouds `idx` (host array)"""
+        if self.lengths_host is None:
+            return np.full(len(idx), self.points.shape[1], dtype=np.int32)
+        return self.lengths_host[idx]
+
+
+class DeviceBatchLoader:
+    """Iterate a DeviceCloudSet in batches made on the device.  Yields device tensors with the shapes and dtypes the reference's
+    default collate gives: (pc [B, npoints, 3] f32, target [B] i64) for "modelnet" / "scanobjectnn", (pc, cls [B, 1] i32,
+    seg [B, npoints] i64) for "shapenetpart" (seg already `.long()`, as main_partseg.py:207 makes it).
+
+    Order: `epoch_indices` -- DistributedSampler(shuffle, seed, drop_last) for (rank, world_size); drop_last also drops an
+    incomplete last batch, as DataLoader(drop_last=True) does.  set_epoch(e) as with the sampler.
+    Batch i + `ahead` is queued on graphs.shared_group_stream() before batch i is yielded.  Every yielded tensor is a fresh allocation
+    made under that stream, record_stream-ed on the consumer's stream, and carries its completion event as `_ppt_ready`
+    (graphs.wait_inputs: the model's input-only stages start behind it on their own stream).  The iteration never synchronises.
+    No stream is created here: see DevicePrefetcher._stream for what a further stream does to the two-stream schedule."""
+
+    def __init__(self, cloud_set, batch_size, npoints, recipe, train, shuffle=True, drop_last=False, seed=0, draws="device", rank=0,
+                 world_size=1, ahead=2):
+        if recipe not in RECIPES:
+            raise ValueError(f"recipe must be one of {RECIPES}, got {recipe!r}")
+        if draws not in ("device", "numpy"):
+            raise ValueError(f"draws must be 'device' or 'numpy', got {draws!r}")
+        if not 1 <= int(npoints) <= MAX_NPOINTS:
+            raise ValueError(f"npoints must be in [1, {MAX_NPOINTS}], got {npoints}")
+        if int(batch_size) < 1 or int(ahead) < 1:
+            raise ValueError("batch_size and ahead must be at least 1")
+        self.set, self.batch_size, self.npoints, self.recipe, self.train = cloud_set, int(batch_size), int(npoints), recipe, bool(train)
+        self.shuffle, self.drop_last, self.seed, self.draws = bool(shuffle), bool(drop_last), int(seed), draws
+        self.rank, self.world_size, self.ahead, self.epoch = int(rank), int(world_size), int(ahead), 0
+        epoch_indices(1, rank=self.rank, world_size=self.world_size)          # validates rank / world_size
+        rows = cloud_set.rows(np.arange(len(cloud_set)))
+        if recipe == "shapenetpart":
+            if cloud_set.seg is None:
+                raise ValueError("recipe 'shapenetpart' needs a DeviceCloudSet with seg")
+        else:
+            if rows.min() < self.npoints:
+                raise ValueError(f"recipe {recipe!r}: every cloud needs at least npoints = {self.npoints} rows (shortest: {rows.min()})")
+            if recipe == "modelnet" and rows.min() != rows.max():
+                raise ValueError("recipe 'modelnet': the batched FPS launch walks one row count for all its clouds; give clouds of one "
+                                 "length (ModelNet's are), e.g. one DeviceCloudSet per length")
+        self._fps_rows = int(rows[0]) if recipe == "modelnet" and rows[0] > self.npoints else 0
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def indices(self):
+        """this rank's dataset indices for the current epoch"""
+        return epoch_indices(len(self.set), self.epoch, self.shuffle, self.seed, self.drop_last, self.rank, self.world_size)
+
+    def __len__(self):
+        n = len(epoch_indices(len(self.set), 0, False, 0, self.drop_last, self.rank, self.world_size))
+        return n // self.batch_size if self.drop_last else math.ceil(n / self.batch_size)
+
+    # ---- one batch, queued on the current (= the grouping) stream ------------------------------------------------------------
+    def _host_draws(self, rs, idx):
+        """numpy mode: the batch's draws in ONE pinned buffer (a single asynchronous copy), viewed per array on the device."""
+        B, n = len(idx), self.npoints
+        rows = self.set.rows(idx)
+        per = [numpy_draws(rs, self.recipe, self.train, int(r), n) for r in rows]
+        parts = {}
+        if "start" in per[0]:
+            parts["start"] = np.asarray([d["start"] for d in per], dtype=np.int64)
+        if "scale" in per[0]:
+            parts["scale"] = np.stack([d["scale"] for d in per]).astype(np.float64)
+            parts["shift"] = np.stack([d["shift"] for d in per]).astype(np.float64)
+        if "sel" in per[0]:
+            parts["sel"] = np.stack([d["sel"] for d in per]).astype(np.int64)
+        if "perm" in per[0]:
+            parts["perm"] = np.stack([d["perm"] for d in per]).astype(np.int32)            # last: the only 4-byte array
+        if not parts:
+            return {}
+        total = sum(a.nbytes for a in parts.values())
+        pin = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        host, off, spans = pin.numpy(), 0, {}
+        for k, a in parts.items():
+            host[off:off + a.nbytes] = a.reshape(-1).view(np.uint8)
+            spans[k] = (off, a.nbytes, a.shape, a.dtype)
+            off += a.nbytes
+        dev = pin.to(self.set.device, non_blocking=True)
+        tdt = {np.dtype(np.int64): torch.int64, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32}
+        return {k: dev[o:o + nb].view(tdt[np.dtype(dt)]).view(*shape) for k, (o, nb, shape, dt) in spans.items()}
+
+    def _produce(self, item, idx, rs):
+        from .. import ops
+        s, n = self.set, self.npoints
+        part = self.recipe == "shapenetpart"
+        if self.draws == "numpy":
+            d = self._host_draws(rs, idx)
+        else:
+            rows = None if s.lengths is None else s.lengths.index_select(0, item)
+            d = ops.cloud_draws(item, n, self.seed, self.epoch, rows=rows, rows_all=s.points.shape[1], start=self._fps_rows > 0,
+                                affine=self.train and not part, perm=self.train and not part, sel=part)
+        sel = d.get("sel")
+        if self._fps_rows:
+            xyz = s.points.index_select(0, item)
+            if xyz.shape[1] != self._fps_rows or xyz.shape[2] != 3:
+                xyz = xyz[:, :self._fps_rows, :3].contiguous()
+            sel, _ = ops.fps(xyz, n, d["start"])
+        out = ops.cloud_prep(s.points, item, n, sel=sel, lengths=s.lengths, normalize=self.recipe == "modelnet", scale=d.get("scale"),
+                             shift=d.get("shift"), perm=d.get("perm"), seg_src=s.seg if part else None)
+        target = s.labels.index_select(0, item)
+        if part:
+            return (out[0], target.to(torch.int32).view(-1, 1), out[1])
+        return (out, target)
+
+    def __iter__(self):
+        from .. import graphs
+        dev = self.set.device
+        if dev.type != "cuda":
+            raise RuntimeError("DeviceBatchLoader runs on the HIP device (libppt_hip.so: ppt_cloud_prep_f32); there is no CPU path")
+        order = self.indices()
+        nb = len(self)
+        group = graphs.shared_group_stream(dev)
+        rs = np.random.RandomState([self.seed, self.epoch, self.rank]) if self.draws == "numpy" else None
+        with torch.cuda.stream(group):
+            order_dev = torch.from_numpy(order).pin_memory().to(dev, non_blocking=True)      # the epoch's order: one copy, up front
+        queue = collections.deque()
+        state = {"next": 0}
+
+        def put():
+            i = state["next"]
+            if i >= nb:
+                return
+            state["next"] = i + 1
+            lo, hi = i * self.batch_size, min((i + 1) * self.batch_size, len(order))
+            with torch.cuda.stream(group):
+                batch = self._produce(order_dev[lo:hi], order[lo:hi], rs)
+                ev = torch.cuda.Event()
+                ev.record(group)
+            for t in batch:
+                t._ppt_ready = ev
+            queue.append((batch, ev))
+        for _ in range(self.ahead):
+            put()
+        while queue:
+            batch, ev = queue.popleft()
+            cur = torch.cuda.current_stream(dev)
+            cur.wait_event(ev)
+            for t in batch:
+                t.record_stream(cur)
+            put()
+            yield batch

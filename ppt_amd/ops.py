@@ -1440,3 +1440,67 @@ def prompt_rows_bwd(g, rows_of, n_tok, scale=1.0):
     _lib.check(_lib.lib().ppt_prompt_rows_bwd(_p(g), _p(rows_of), rows_of.shape[1], n_tok, W, float(scale), _p(out), _stream()),
                "ppt_prompt_rows_bwd")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# the device-resident input pipeline (csrc/cloud_prep.hip; ppt_amd/data/device_loader.py)
+def cloud_prep(src, item, n, *, sel=None, lengths=None, normalize=False, scale=None, shift=None, perm=None, seg_src=None):
+    """src [M, Nmax, C >= 3] f32 resident clouds, item [B] i64 -> out [B, n, 3] f32 (and seg [B, n] i64 when seg_src [M, Nmax] i32
+    is given): rows `sel` [B, n] i64 (None: the first n) of cloud item[b], pc_normalize if `normalize`, translate_pointcloud when
+    scale / shift [B, 3] f64 are given, np.random.shuffle when perm [B, n] i32 is -- bit-identical to the reference's numpy
+    (ppt_cloud_prep_f32)."""
+    _chk(src, torch.float32, "src"); _chk(item, torch.int64, "item"); _chk(sel, torch.int64, "sel"); _chk(lengths, torch.int32, "lengths")
+    _chk(scale, torch.float64, "scale"); _chk(shift, torch.float64, "shift"); _chk(perm, torch.int32, "perm")
+    _chk(seg_src, torch.int32, "seg_src")
+    if src.dim() != 3:
+        raise ValueError(f"src must be [M, Nmax, C], got {tuple(src.shape)}")
+    M, Nmax, C = src.shape
+    B = item.numel()
+    for t, shape, nm in ((sel, (B, n), "sel"), (perm, (B, n), "perm"), (scale, (B, 3), "scale"), (shift, (B, 3), "shift"),
+                         (lengths, (M,), "lengths"), (seg_src, (M, Nmax), "seg_src")):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{nm} must be {shape}, got {tuple(t.shape)}")
+    if (scale is None) != (shift is None):
+        raise ValueError("scale and shift are given together")
+    out = torch.empty((B, n, 3), dtype=torch.float32, device=src.device)
+    seg = torch.empty((B, n), dtype=torch.int64, device=src.device) if seg_src is not None else None
+    if profiler is not None:
+        profiler.begin("cloud_prep", float(B) * n * (24 + (8 if sel is not None else 0) + (4 if perm is not None else 0)))
+    _lib.check(_lib.lib().ppt_cloud_prep_f32(_p(src), M, Nmax, C, _p(lengths), _p(item), B, _p(sel), int(n), int(bool(normalize)),
+                                             int(scale is not None), _p(scale), _p(shift), _p(perm), _p(seg_src), _p(seg), _p(out),
+                                             _stream()), "ppt_cloud_prep_f32")
+    if profiler is not None:
+        profiler.end()
+    return out if seg is None else (out, seg)
+
+
+def cloud_draws(index, n, seed, epoch, *, rows=None, rows_all=0, start=False, affine=False, perm=False, sel=False):
+    """The Philox4x32-10 draws of the samples `index` [B] i64 (ppt_cloud_draws): a dict with the requested ones of
+    start [B] i64 and sel [B, n] i64 in [0, rows), scale / shift [B, 3] f64, perm [B, n] i32.  rows [B] i32 or rows_all."""
+    _chk(index, torch.int64, "index"); _chk(rows, torch.int32, "rows")
+    B, dev = index.numel(), index.device
+    out = {}
+    if start:
+        out["start"] = torch.empty(B, dtype=torch.int64, device=dev)
+    if affine:
+        out["scale"] = torch.empty((B, 3), dtype=torch.float64, device=dev)
+        out["shift"] = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    if perm:
+        out["perm"] = torch.empty((B, n), dtype=torch.int32, device=dev)
+    if sel:
+        out["sel"] = torch.empty((B, n), dtype=torch.int64, device=dev)
+    g = out.get
+    _lib.check(_lib.lib().ppt_cloud_draws(_p(index), B, _p(rows), int(rows_all), int(n), int(seed) & (2 ** 64 - 1), int(epoch) & 0xFFFFFFFF,
+                                          _p(g("start")), _p(g("scale")), _p(g("shift")), _p(g("perm")), _p(g("sel")), None, 0, None,
+                                          _stream()), "ppt_cloud_draws")
+    return out
+
+
+def philox4x32(counters, seed):
+    """counters [R, 4] i32 (the bit patterns of the 32-bit counter words) -> the Philox4x32-10 output words [R, 4] i32 under the
+    64-bit key `seed` (low word = key[0]): the generator of ppt_cloud_draws, exposed for known-answer checks."""
+    _chk(counters, torch.int32, "counters")
+    out = torch.empty_like(counters)
+    _lib.check(_lib.lib().ppt_cloud_draws(None, 0, None, 0, 0, int(seed) & (2 ** 64 - 1), 0, None, None, None, None, None, _p(counters),
+                                          counters.shape[0], _p(out), _stream()), "ppt_cloud_draws")
+    return out
