@@ -45,8 +45,8 @@ const char *ppt_strerror(int code);
  * 7: ppt_gemm_params.split_overflow (new trailing field: split16 saturates finite values beyond IEEE half's range and counts
  *    the workgroups that did), ppt_vit_mlp3_bf16 / ppt_vit_mlp3_retile (new: csrc/mlp_fused3.hip), ppt_text_mlp_pair /
  *    ppt_text_mlp_retile (new: csrc/text_mlp.hip), ppt_lnlin / ppt_lnlin_retile (new: csrc/lnlin.hip),
- *    ppt_text_mlp_retile_split + the split16 fields of ppt_text_mlp_params (csrc/text_mlp_split.hip), ppt_text_lin_split /
- *    ppt_text_lin_retile_split (csrc/text_lin_split.hip); later, additive only (no existing signature or struct changed):
+ *    ppt_text_mlp_retile_split + the split16 fields of ppt_text_mlp_params (csrc/text_mlp.hip), ppt_text_lin_split /
+ *    ppt_text_lin_retile_split (csrc/text_lin.hip); later, additive only (no existing signature or struct changed):
  *    ppt_text_lin16 / ppt_text_lin_retile16 (the 16-bit form of ppt_text_lin_split); ppt_cloud_prep_f32 / ppt_cloud_draws (csrc/cloud_prep.hip).
  * 6: ppt_gemm_params.split16 / split_a_pow2 / split_b_pow2 (new trailing fields: fp32 operands as hi + lo half pairs),
  *    ppt_attention_fwd_split16 / ppt_attention_bwd_split16 (new), ppt_pointmlp_cloud_rstd / ppt_pointmlp_pq (new).
@@ -357,7 +357,7 @@ typedef struct ppt_text_mlp_params {
      * LayerNorm(A; ln_w, ln_b, ln_eps) -- ln_2 of the layer, computed in fp32 as ULIP_models.py:21-27 does -- is applied while the rows
      * are staged; ln_mean / ln_rstd [M] (optional) receive the row statistics for the LayerNorm backward. */
     const float *ln_w; const float *ln_b; float ln_eps; float *ln_mean; float *ln_rstd;
-    /* dtype == PPT_F32: the split16 form (csrc/text_mlp_split.hip) -- A and `pre` are fp32, W1 / W2 the hi + lo half copies of
+    /* dtype == PPT_F32: the split16 form (csrc/text_mlp.hip) -- A and `pre` are fp32, W1 / W2 the hi + lo half copies of
      * ppt_text_mlp_retile_split (made with the same split_b_pow2), every product three MFMAs on hi + lo IEEE-half pairs
      * (ppt_gemm_params.split16); A and the hidden activation are multiplied by 2^split_a_pow2 before they are split; a wave that
      * saturated a finite value beyond half's range adds 1 to *split_overflow (may be NULL).  The LayerNorm prologue as above. */
@@ -368,7 +368,7 @@ int ppt_text_mlp_retile(const void *W1, const void *W2, void *W1_tiled, void *W2
 int ppt_text_mlp_retile_split(const float *W1, const float *W2, void *W1_tiled, void *W2_tiled, int b_pow2, void *stream);
 int ppt_text_mlp_pair(const ppt_text_mlp_params *p, void *stream);
 
-/* ---- one linear of the text tower's attention half on split16 products, rows stationary (ABI 7; csrc/text_lin_split.hip) -------
+/* ---- one linear of the text tower's attention half on split16 products, rows stationary (ABI 7; csrc/text_lin.hip) -------
  * C[M, N] = A[M, K] W[N, K]^T (+ bias) (+ residual), every product three MFMAs on hi + lo IEEE-half pairs of the fp32 operands
  * (ppt_gemm_params.split16): nn.MultiheadAttention's in_proj / out_proj of a CLIP ResidualAttentionBlock (ULIP_models.py:38, 45-51)
  * and their input-gradient products.  K a multiple of 512, N of 256.  K > 512: the K chunks' partial products leave separately,
@@ -386,7 +386,7 @@ typedef struct ppt_text_lin_params {
 } ppt_text_lin_params;
 int ppt_text_lin_retile_split(const float *W, void *W_tiled, int N, int K, int b_pow2, void *stream);
 int ppt_text_lin_split(const ppt_text_lin_params *p, void *stream);
-/* ... and its form on the mixed mode's 16-bit operands (ABI 7, additive; csrc/text_lin_split.hip): C[M, N] = A[M, K] W[N, K]^T
+/* ... and its form on the mixed mode's 16-bit operands (ABI 7, additive; csrc/text_lin.hip): C[M, N] = A[M, K] W[N, K]^T
  * (+ bias) (+ residual), one MFMA per 16-bit fragment, fp32 accumulation.  C is fp32 (c_dtype PPT_F32) or `dtype` (rounded as
  * ppt_gemm rounds: beyond the format's range is +-inf).  K a multiple of 512, N of 256; K > 512: the K chunks' fp32 partial products
  * parts[K / 512][M][N] (c_dtype PPT_F32, ldc == N, no bias / residual).  W: the fragment-ordered copy of ppt_text_lin_retile16

@@ -318,6 +318,22 @@ __device__ __forceinline__ float split_saturate(float x, uint32_t &over)
     return cut ? copysignf(HALF_MAX, x) : x;
 }
 
+// four fp32 values (already scaled and saturated) -> 8 bytes of hi halves, 8 bytes of lo halves
+__device__ __forceinline__ void split4(const float (&x)[4], uint2 &H, uint2 &L)
+{
+    uint32_t h[2], l[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const _Float16 h0 = (_Float16)x[2 * q], h1 = (_Float16)x[2 * q + 1];
+        const ppt_h2 hh = {h0, h1};
+        const ppt_h2 ll = {(_Float16)(x[2 * q] - (float)h0), (_Float16)(x[2 * q + 1] - (float)h1)};
+        h[q] = __builtin_bit_cast(uint32_t, hh);
+        l[q] = __builtin_bit_cast(uint32_t, ll);
+    }
+    H = make_uint2(h[0], h[1]);
+    L = make_uint2(l[0], l[1]);
+}
+
 template <int NR, int ROWS, int STRIDE = 32>                 // STRIDE = threads / 8: rows one pass of the workgroup covers
 __device__ __forceinline__ void write_stage_split(const Stage<NR> &st, unsigned char *tile, float s, uint32_t &over)
 {

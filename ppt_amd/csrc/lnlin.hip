@@ -21,8 +21,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-
 constexpr int D = 384, NC = 384;                                   // K, columns per workgroup
 constexpr int RB = 4, R = 16 * RB;                                 // row blocks / rows per workgroup
 constexpr int AP = 2 * D + 32;                                     // image pitch (bytes): = 32 mod 256 -> conflict-free b128 fragment reads
@@ -32,22 +30,6 @@ static_assert(R * CP <= LDS_BYTES, "the C tile must fit where the image was");
 constexpr int KS = D / 32;                                         // k-steps (12)
 constexpr int DR = 3;                                              // ring depth in k-steps (divides 12; 4 -> 128 VGPRs with 4 spilled)
 constexpr int WAVE_SLICE = KS * 3 * 1024;                          // bytes of one wave's fragments per slice (36 KiB)
-
-__device__ __forceinline__ float row16_sum_l(float v)
-{
-    v += __uint_as_float(dpp_mov<0xB1, 0xf>(__float_as_uint(v)));
-    v += __uint_as_float(dpp_mov<0x4E, 0xf>(__float_as_uint(v)));
-    v += __uint_as_float(dpp_mov<0x141, 0xf>(__float_as_uint(v)));
-    v += __uint_as_float(dpp_mov<0x140, 0xf>(__float_as_uint(v)));
-    return v;
-}
-
-__device__ __forceinline__ void lds_barrier_l()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // Diagnostic build only (tools/lnlin_stamp.py compiles this file with -DPPT_LNLIN_STAMP into its own library): lane 0 of every wave stores
 // s_memtime at its phase boundaries into the buffer passed as `bias`: [workgroup][wave][8].
@@ -107,14 +89,14 @@ __global__ __launch_bounds__(512, 4) void lnlin_kernel(const ppt_lnlin_params p)
             float sm = 0.f;
 #pragma unroll
             for (int i = 0; i < D / 64; ++i) sm += (xf[pass][i].x + xf[pass][i].y) + (xf[pass][i].z + xf[pass][i].w);
-            const float mean = row16_sum_l(sm) * (1.0f / (float)D);
+            const float mean = row16_sum(sm) * (1.0f / (float)D);
             float q = 0.f;
 #pragma unroll
             for (int i = 0; i < D / 64; ++i) {
                 const float d0 = xf[pass][i].x - mean, d1 = xf[pass][i].y - mean, d2 = xf[pass][i].z - mean, d3 = xf[pass][i].w - mean;
                 q = fmaf(d0, d0, q); q = fmaf(d1, d1, q); q = fmaf(d2, d2, q); q = fmaf(d3, d3, q);
             }
-            const float rstd = 1.0f / sqrtf(row16_sum_l(q) * (1.0f / (float)D) + p.ln_eps);
+            const float rstd = 1.0f / sqrtf(row16_sum(q) * (1.0f / (float)D) + p.ln_eps);
             unsigned char *dst = smem + lr * AP;
 #pragma unroll
             for (int i = 0; i < D / 64; ++i) {
@@ -129,15 +111,15 @@ __global__ __launch_bounds__(512, 4) void lnlin_kernel(const ppt_lnlin_params p)
         }
     }
     LNLIN_STAMP(2);
-    lds_barrier_l();
+    lds_barrier();
     LNLIN_STAMP(3);
 
     // ---- C^T[n][m] = W[n][k] image[m][k]: a lane holds four consecutive columns of a row
-    f32x4_t acc[RB][3];
+    ppt_f32x4 acc[RB][3];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-        for (int nb = 0; nb < 3; ++nb) acc[rb][nb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int nb = 0; nb < 3; ++nb) acc[rb][nb] = ppt_f32x4{0.f, 0.f, 0.f, 0.f};
     {
         const unsigned char *ha = smem + l15 * AP + 16 * kg;
         uint4 fa[2][RB];
@@ -158,7 +140,7 @@ __global__ __launch_bounds__(512, 4) void lnlin_kernel(const ppt_lnlin_params p)
         }
     }
     LNLIN_STAMP(4);
-    lds_barrier_l();                                                     // every wave is done reading the image
+    lds_barrier();                                                     // every wave is done reading the image
     LNLIN_STAMP(5);
 
     // ---- (+ bias) -> the C tile in LDS -> 16-byte row pieces
@@ -173,7 +155,7 @@ __global__ __launch_bounds__(512, 4) void lnlin_kernel(const ppt_lnlin_params p)
                     make_uint2(h16<F>::pack2(acc[rb][nb][0] + bv.x, acc[rb][nb][1] + bv.y), h16<F>::pack2(acc[rb][nb][2] + bv.z, acc[rb][nb][3] + bv.w));
         }
     }
-    lds_barrier_l();
+    lds_barrier();
     LNLIN_STAMP(6);
     {
         constexpr int CPR = NC / 8;                                       // 16-byte pieces per row (48)

@@ -30,8 +30,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-
 constexpr int D = 384, HID = 1536, HC = 128, NJ = HID / HC;       // model dims, hidden slab
 #ifndef PPT_MLP_RB
 #define PPT_MLP_RB 5
@@ -40,15 +38,6 @@ constexpr int RB = PPT_MLP_RB, R = 16 * RB;                        // row blocks
 constexpr int HP = 2 * D + 32, UP = 2 * HC + 32;                   // LDS pitches (bytes): = 32 mod 256 -> conflict-free b128 fragment reads
 constexpr int H2_BYTES = R * HP, U_BYTES = R * UP;
 constexpr int LDS_BYTES = H2_BYTES + 2 * U_BYTES + (2 * D + HID + D) * 4;
-
-__device__ __forceinline__ float row16_sum(float v)
-{
-    v += __uint_as_float(dpp_mov<0xB1, 0xf>(__float_as_uint(v)));
-    v += __uint_as_float(dpp_mov<0x4E, 0xf>(__float_as_uint(v)));
-    v += __uint_as_float(dpp_mov<0x141, 0xf>(__float_as_uint(v)));
-    v += __uint_as_float(dpp_mov<0x140, 0xf>(__float_as_uint(v)));
-    return v;
-}
 
 // Diagnostic build only (tools/mlp_stamp.py compiles this file with -DPPT_MLP_STAMP): s_memtime stamps of the first chunk's
 // phases go to the buffer passed in `residual2`: [workgroup][wave][slab 0..11 + 2][8].
@@ -113,11 +102,11 @@ __global__ __launch_bounds__(512, 2) void vit_mlp_kernel(const ppt_vit_mlp_param
             auto pfrag = [&](int nb, int ks) {
                 return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(wrs, lane * 16, (w * 36 + nb * 12 + ks) * 1024, 0));
             };
-            f32x4_t pa[RB][3];
+            ppt_f32x4 pa[RB][3];
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-                for (int nb = 0; nb < 3; ++nb) pa[rb][nb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+                for (int nb = 0; nb < 3; ++nb) pa[rb][nb] = ppt_f32x4{0.f, 0.f, 0.f, 0.f};
             {
                 uint4 wf[4][3];
 #pragma unroll
@@ -251,19 +240,19 @@ __global__ __launch_bounds__(512, 2) void vit_mlp_kernel(const ppt_vit_mlp_param
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
 
-        f32x4_t acc2[RB][3];
+        ppt_f32x4 acc2[RB][3];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-            for (int nb = 0; nb < 3; ++nb) acc2[rb][nb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            for (int nb = 0; nb < 3; ++nb) acc2[rb][nb] = ppt_f32x4{0.f, 0.f, 0.f, 0.f};
 
         // The weights of the NEXT use are fetched inside the MFMA loop of the CURRENT phase, one load per MFMA group: issued
         // as a burst after the loop (first version) the twelve loads stalled the wave ~2 500 cycles at the issue stage while
         // the matrix pipe sat idle (in-kernel stamps).  jb >= 0: load B2 fragments of slab jb (gemm1) / B1 of slab jb (gemm2).
         auto gemm1 = [&](int j, int jb) {                               // -> slab j in ub[j & 1]
-            f32x4_t a1[RB];
+            ppt_f32x4 a1[RB];
 #pragma unroll
-            for (int rb = 0; rb < RB; ++rb) a1[rb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            for (int rb = 0; rb < RB; ++rb) a1[rb] = ppt_f32x4{0.f, 0.f, 0.f, 0.f};
             const unsigned char *ha = h2 + l15 * HP + 16 * kg;
 #pragma unroll
             for (int s = 0; s < D / 32; ++s) {

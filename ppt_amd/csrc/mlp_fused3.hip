@@ -24,8 +24,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-
 constexpr int D = 384, HID = 1536, HC = 256, NJ = HID / HC;       // model dims, hidden slab
 constexpr int RB = 5, R = 16 * RB;                                 // row blocks / rows per chunk
 constexpr int HP = 2 * D + 32, UP = 2 * HC + 32;                   // LDS pitches (bytes): = 32 mod 256 -> conflict-free b128 fragment reads
@@ -42,15 +40,6 @@ constexpr int D1 = PPT_MLP3_D1, D2 = PPT_MLP3_D2;                  // ring depth
 static_assert(K1 % D1 == 0 && K2 % D2 == 0, "ring slots must line up from slab to slab");
 static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 constexpr int W1_BYTES = HID * D * 2, W2_BYTES = D * HID * 2;
-
-__device__ __forceinline__ float row16_sum3(float v)
-{
-    v += __uint_as_float(dpp_mov<0xB1, 0xf>(__float_as_uint(v)));
-    v += __uint_as_float(dpp_mov<0x4E, 0xf>(__float_as_uint(v)));
-    v += __uint_as_float(dpp_mov<0x141, 0xf>(__float_as_uint(v)));
-    v += __uint_as_float(dpp_mov<0x140, 0xf>(__float_as_uint(v)));
-    return v;
-}
 
 // GELU (exact-erf form as an odd polynomial, ppt_act.h) with the saturation folded into a clamp of the erf argument: the
 // polynomial was fitted on |x| < 4 and erf(4 / sqrt 2) = 0.99994, so clamping x to [-4, 4] for the erf factor replaces gelu_poly's
@@ -70,17 +59,6 @@ __device__ __forceinline__ float gelu_poly3(float x, float hs)
     const float e = p * xc;
     const float h = hs * x;
     return fmaf(h, e, h);
-}
-
-// A workgroup barrier for LDS hand-overs ONLY: the LDS operations of this wave are complete (lgkmcnt(0)), global loads stay in
-// flight.  __syncthreads() is a workgroup-scope release + acquire around s_barrier, i.e. s_waitcnt vmcnt(0): every barrier of the
-// slab loop drained the weight rings (in-kernel stamps: ~1 200 cycles per slab at the barrier), and the barrier at the end of the
-// prologue waited for the ring fill it was meant to overlap.  Nothing in this kernel hands GLOBAL data from wave to wave.
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
 }
 
 #ifdef PPT_MLP3_STAMP
@@ -146,7 +124,7 @@ __global__ __launch_bounds__(512, 2) void vit_mlp3_kernel(const ppt_vit_mlp_para
         // The residual rows are requested FIRST, in this layout, and nothing else reads x: the LayerNorm statistics are formed from
         // the accumulator layout too (first version: a separate 16-threads-per-row LayerNorm pass over x in three dependent
         // load -> reduce -> write rounds, then a second read of x for the accumulators -- 41 000 cycles of prologue per chunk).
-        f32x4_t acc2[RB][3];
+        ppt_f32x4 acc2[RB][3];
         float hrs[RB], rs1[RB];
         uint4 g1[D1][2], g2[D2][3];                                      // the two weight rings
         {
@@ -210,7 +188,7 @@ __global__ __launch_bounds__(512, 2) void vit_mlp3_kernel(const ppt_vit_mlp_para
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-                    for (int nb = 0; nb < 3; ++nb) acc2[rb][nb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+                    for (int nb = 0; nb < 3; ++nb) acc2[rb][nb] = ppt_f32x4{0.f, 0.f, 0.f, 0.f};
                 const unsigned char *ha = h2 + l15 * HP + 16 * kg;
                 uint4 fp[2][RB];                                          // (the image fragments of k-step ks + 1 requested before the MFMAs of k-step ks: GEMM1 below)
 #pragma unroll
@@ -248,7 +226,7 @@ __global__ __launch_bounds__(512, 2) void vit_mlp3_kernel(const ppt_vit_mlp_para
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-                    for (int nb = 0; nb < 3; ++nb) acc2[rb][nb] = f32x4_t{xv[rb][nb].x, xv[rb][nb].y, xv[rb][nb].z, xv[rb][nb].w};
+                    for (int nb = 0; nb < 3; ++nb) acc2[rb][nb] = ppt_f32x4{xv[rb][nb].x, xv[rb][nb].y, xv[rb][nb].z, xv[rb][nb].w};
             }
         }
         MLP3_STAMP(5, 5);
@@ -323,7 +301,7 @@ __global__ __launch_bounds__(512, 2) void vit_mlp3_kernel(const ppt_vit_mlp_para
         MLP3_STAMP(6, 1);
         RELANE();
 
-        f32x4_t a1[RB][2];
+        ppt_f32x4 a1[RB][2];
         // GEMM1(jj): a1 = W1[slab jj, this wave's 32 units] . H2^T -- every H2 fragment feeds two MFMAs; the ring slot a k-step used
         // is refilled with the k-step D1 further on (of the next slab -- of slab 0 behind the last: the next chunk's -- past the end)
         auto gemm1 = [&](int jj) {
@@ -331,7 +309,7 @@ __global__ __launch_bounds__(512, 2) void vit_mlp3_kernel(const ppt_vit_mlp_para
             for (int h = 0; h < 2; ++h) {                                 // the accumulators START at the fc1 bias (a lane's four hidden units)
                 const float4 bv = *reinterpret_cast<const float4 *>(b1s + jj * HC + 32 * w + 16 * h + 4 * kg);
 #pragma unroll
-                for (int rb = 0; rb < RB; ++rb) a1[rb][h] = f32x4_t{bv.x, bv.y, bv.z, bv.w};
+                for (int rb = 0; rb < RB; ++rb) a1[rb][h] = ppt_f32x4{bv.x, bv.y, bv.z, bv.w};
             }
             const unsigned char *ha = h2 + l15 * HP + 16 * kg;
             // the H2 fragments of k-step ks + 1 are requested before the MFMAs of k-step ks (two register sets): left to itself hipcc

@@ -118,6 +118,28 @@ __device__ __forceinline__ uint32_t dpp_mov(uint32_t v)
     return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xf, false);
 }
 
+// sum over the 16 lanes of a DPP row; every lane gets the same bits (each step adds a value to its mirror image)
+__device__ __forceinline__ float row16_sum(float v)
+{
+    v += __uint_as_float(dpp_mov<0xB1, 0xf>(__float_as_uint(v)));       // quad_perm [1,0,3,2]
+    v += __uint_as_float(dpp_mov<0x4E, 0xf>(__float_as_uint(v)));       // quad_perm [2,3,0,1]
+    v += __uint_as_float(dpp_mov<0x141, 0xf>(__float_as_uint(v)));      // row_half_mirror
+    v += __uint_as_float(dpp_mov<0x140, 0xf>(__float_as_uint(v)));      // row_mirror
+    return v;
+}
+
+// A workgroup barrier for LDS hand-overs ONLY (the rows-stationary kernels: mlp_fused3, lnlin, text_lin, text_mlp): the LDS operations
+// of this wave are complete (lgkmcnt(0)), global loads stay in flight.  __syncthreads() is a workgroup-scope release + acquire around
+// s_barrier, i.e. s_waitcnt vmcnt(0): every barrier of mlp_fused3's slab loop drained the weight rings (in-kernel stamps: ~1 200
+// cycles per slab at the barrier), and the barrier at the end of the prologue waited for the ring fill it was meant to overlap.
+// Not for kernels that hand GLOBAL data from wave to wave.
+__device__ __forceinline__ void lds_barrier()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
 // Cross-half (lane ^ 32) reductions on v_permlane32_swap, with explicit wait states.  Found the hard way
 // (tools/gemm_determinism.py): when hipcc (ROCm 7.2) feeds the swap from a chain of packed-fp32 ops (v_pk_add_f32 ...
 // s_nop 0, v_mov, s_nop 1, v_permlane32_swap, VALU read) the BatchNorm chunk sums came out wrong in lanes 16-31 of

@@ -28,8 +28,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-
 template <int K> struct RG {
     static constexpr int NCB = (K == 384) ? 3 : 2;      // 16-column blocks per wave
     static constexpr int NW = 16 * NCB;                  // columns per wave
@@ -43,16 +41,6 @@ template <int K> struct RG {
     static constexpr int CBUF = 32 * CPITCH;
     static constexpr int LDS = 2 * BUF + 2 * K * 4 + NB * 4 + 2 * CBUF;   // two A buffers, gamma, beta, the bias slice, two C tiles
 };
-
-// sum over the 16 lanes of a DPP row; every lane gets the same bits (each step adds a value to its mirror image)
-__device__ __forceinline__ float row16_sum(float v)
-{
-    v += __uint_as_float(dpp_mov<0xB1, 0xf>(__float_as_uint(v)));       // quad_perm [1,0,3,2]
-    v += __uint_as_float(dpp_mov<0x4E, 0xf>(__float_as_uint(v)));       // quad_perm [2,3,0,1]
-    v += __uint_as_float(dpp_mov<0x141, 0xf>(__float_as_uint(v)));      // row_half_mirror
-    v += __uint_as_float(dpp_mov<0x140, 0xf>(__float_as_uint(v)));      // row_mirror
-    return v;
-}
 
 enum { EPI_BF16 = 0, EPI_RESIDUAL = 1 };
 // Diagnostic build only (tools/rowgemm_stamp.py compiles this file with -DPPT_RG_STAMP into its own library): every wave
@@ -185,14 +173,14 @@ __global__ __launch_bounds__(512, 2) void rowgemm_kernel(const ppt_rowgemm_param
         }
     };
 
-    f32x4_t acc[2][G::NCB];
+    ppt_f32x4 acc[2][G::NCB];
     auto mfma_phase = [&](int cur) {
         const unsigned char *a0 = smem + cur * G::BUF + l15 * G::PITCH + 16 * kg;
         const unsigned char *a1 = a0 + 16 * G::PITCH;
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-            for (int nb = 0; nb < G::NCB; ++nb) acc[rb][nb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            for (int nb = 0; nb < G::NCB; ++nb) acc[rb][nb] = ppt_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < G::KS; ++s) {
             const uint4 f0 = *reinterpret_cast<const uint4 *>(a0 + 64 * s);

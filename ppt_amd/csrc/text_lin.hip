@@ -1,5 +1,5 @@
-// text_lin_split.hip -- ONE linear of the CLIP text tower's attention half, rows stationary and the weight streamed -- the first
-// product of csrc/text_mlp_split.hip / csrc/text_mlp.hip as a launch of its own.  On the prompt chain (817 rows with the shared
+// text_lin.hip -- ONE linear of the CLIP text tower's attention half, rows stationary and the weight streamed -- the first
+// product of csrc/text_mlp.hip as a launch of its own.  On the prompt chain (817 rows with the shared
 // prefix) these are in_proj (512 -> 1536), out_proj (512 -> 512, + bias + residual) and their two input-gradient products
 // (512 -> 512; 1536 -> 512 as three K chunks whose partial products the LayerNorm backward adds up, as it did for the split-K tile
 // GEMM): 48 of the chain's tile GEMMs per step -- 64 x 64 tiles whose K loop pays a global round trip and a barrier per 32 k.
@@ -19,8 +19,6 @@
 #include "gemm_common.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 constexpr int KC = 512;                                            // K chunk
 constexpr int RB = 2, R = 16 * RB;
@@ -53,28 +51,6 @@ template <> struct LinForm<PPT_F32> {
     static constexpr int PARTS = 2;
     static constexpr int D1 = 4;
 };
-
-__device__ __forceinline__ void lds_barrier_l2()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ void split4_l(const float (&x)[4], uint2 &H, uint2 &L)
-{
-    uint32_t h[2], l[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const _Float16 h0 = (_Float16)x[2 * q], h1 = (_Float16)x[2 * q + 1];
-        const ppt_h2 hh = {h0, h1};
-        const ppt_h2 ll = {(_Float16)(x[2 * q] - (float)h0), (_Float16)(x[2 * q + 1] - (float)h1)};
-        h[q] = __builtin_bit_cast(uint32_t, hh);
-        l[q] = __builtin_bit_cast(uint32_t, ll);
-    }
-    H = make_uint2(h[0], h[1]);
-    L = make_uint2(l[0], l[1]);
-}
 
 // NH = column halves of 16 a wave owns: 2 (SLN = 256) or 1 (SLN = 128)
 template <int NH, int FORM>
@@ -138,7 +114,7 @@ __global__ __launch_bounds__(512, 2) void text_lin_kernel(const LinArgs p)
             const float x[4] = {split_saturate(v[it].x * sa, over), split_saturate(v[it].y * sa, over),
                                 split_saturate(v[it].z * sa, over), split_saturate(v[it].w * sa, over)};
             uint2 H, L;
-            split4_l(x, H, L);
+            split4(x, H, L);
             *reinterpret_cast<uint2 *>(ai + lr * AP + 8 * c4) = H;
             *reinterpret_cast<uint2 *>(ai + A_BYTES + lr * AP + 8 * c4) = L;
         }
@@ -162,13 +138,13 @@ __global__ __launch_bounds__(512, 2) void text_lin_kernel(const LinArgs p)
             rv[rb][h] = p.residual ? *reinterpret_cast<const float4 *>(p.residual + (size_t)m * p.ld_res + ncol + 16 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
-    lds_barrier_l2();
+    lds_barrier();
 
-    f32x4_t a1[RB][NH];
+    ppt_f32x4 a1[RB][NH];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-        for (int h = 0; h < NH; ++h) a1[rb][h] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int h = 0; h < NH; ++h) a1[rb][h] = ppt_f32x4{0.f, 0.f, 0.f, 0.f};
     {
         const unsigned char *ha = ai + l15 * AP + 16 * kg;
         uint4 fh[2][RB], fl[2][RB];
@@ -250,8 +226,8 @@ __global__ __launch_bounds__(256) void text_lin_retile_split_kernel(const float 
     const float x0[4] = {split_saturate(a.x * sb, over), split_saturate(a.y * sb, over), split_saturate(a.z * sb, over), split_saturate(a.w * sb, over)};
     const float x1[4] = {split_saturate(b.x * sb, over), split_saturate(b.y * sb, over), split_saturate(b.z * sb, over), split_saturate(b.w * sb, over)};
     uint2 h0, l0, h1, l1;
-    split4_l(x0, h0, l0);
-    split4_l(x1, h1, l1);
+    split4(x0, h0, l0);
+    split4(x1, h1, l1);
     unsigned char *dst = Wt + (size_t)(sc * 8 + w) * (K1 * NH * 2048) + (size_t)f * 2048 + lane * 16;
     *reinterpret_cast<uint4 *>(dst) = make_uint4(h0.x, h0.y, h1.x, h1.y);
     *reinterpret_cast<uint4 *>(dst + 1024) = make_uint4(l0.x, l0.y, l1.x, l1.y);

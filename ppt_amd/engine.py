@@ -876,12 +876,12 @@ POINTMLP_FUSED_NORM = os.environ.get("PPT_POINTMLP_FUSED_NORM", "1") != "0"
 TEXT_MLP_PAIR = os.environ.get("PPT_TEXT_MLP_PAIR", "1") != "0"
 TEXT_MLP_PAIR_LN = os.environ.get("PPT_TEXT_MLP_PAIR_LN", "1") != "0"      # ln_2 inside that launch (forward); 0: its own launch in front
 TEXT_MLP_PAIR_LAST = os.environ.get("PPT_TEXT_MLP_PAIR_LAST", "1") != "0"  # the last layer's forward too (its slices summed by an extra LayerNorm launch)
-# ... and its split16 form (csrc/text_mlp_split.hip) where the text tower runs on fp32 operands as hi + lo half pairs: the whole-model
+# ... and its split16 form (the same kernel template) where the text tower runs on fp32 operands as hi + lo half pairs: the whole-model
 # split16 mode, and the mixed mode on weights whose text tower failed its self-check (checkpoint-like magnitudes).  0: the tile GEMMs.
 TEXT_MLP_PAIR_SPLIT = os.environ.get("PPT_TEXT_MLP_PAIR_SPLIT", "1") != "0"
 
 
-# The attention half's four linears of a text layer on csrc/text_lin_split.hip (rows stationary, weight streamed): in_proj, out_proj
+# The attention half's four linears of a text layer on csrc/text_lin.hip (rows stationary, weight streamed): in_proj, out_proj
 # (+ bias + residual), and their input-gradient products -- in the split16 form (fp32 operands as hi + lo half pairs) and, where the
 # split-K hand-over runs, in the 16-bit form of the mixed mode.  Supported switch: 0 restores the tile GEMMs.
 TEXT_LIN_SPLIT = os.environ.get("PPT_TEXT_LIN_SPLIT", "1") != "0"
@@ -917,16 +917,27 @@ def _text_mlp_pair_ok(Tm):
 
 def _text_mlp_tiles(sd, p, wcm, backward):
     """The fragment-ordered weight copies of layer `p` for ops.text_mlp_pair: forward (c_fc.weight, c_proj.weight); backward the
-    transposed pair (c_proj.weight^T [2048, 512], c_fc.weight^T [512, 2048]) -- the dX operands the WeightCache already keeps."""
+    transposed pair (c_proj.weight^T [2048, 512], c_fc.weight^T [512, 2048]) -- the dX operands the WeightCache already keeps.
+    split16 (wcm holds fp32): the hi + lo half copies, made with the B pre-scale in force (a new fit re-makes them)."""
     wfc, wpr = sd[p + "mlp.c_fc.weight"], sd[p + "mlp.c_proj.weight"]
-    if wcm.dtype == torch.float32:          # split16: hi + lo half copies, made with the B pre-scale in force (a new fit re-makes them)
-        b = ops.SPLIT16_POW2[1]
-        if backward:
-            return wcm.derived(("text_mlp_split_bwd", p, b), (wfc, wpr), lambda: ops.text_mlp_retile_split(wcm.get(wpr, "wt"), wcm.get(wfc, "wt"), b))
-        return wcm.derived(("text_mlp_split_fwd", p, b), (wfc, wpr), lambda: ops.text_mlp_retile_split(wcm.get(wfc), wcm.get(wpr), b))
+    b = ops.SPLIT16_POW2[1] if wcm.dtype == torch.float32 else None
     if backward:
-        return wcm.derived(("text_mlp_tiles_bwd", p), (wfc, wpr), lambda: ops.text_mlp_retile(wcm.get(wpr, "wt"), wcm.get(wfc, "wt")))
-    return wcm.derived(("text_mlp_tiles_fwd", p), (wfc, wpr), lambda: ops.text_mlp_retile(wcm.get(wfc), wcm.get(wpr)))
+        return wcm.derived(("text_mlp_tiles_bwd", p, b), (wfc, wpr), lambda: ops.text_mlp_retile(wcm.get(wpr, "wt"), wcm.get(wfc, "wt"), b))
+    return wcm.derived(("text_mlp_tiles_fwd", p, b), (wfc, wpr), lambda: ops.text_mlp_retile(wcm.get(wfc), wcm.get(wpr), b))
+
+
+def _text_mlp(a, sd, p, wcm, *, pre=None, backward=False, save=False):
+    """The MLP half of layer `p` on ops.text_mlp_pair in wcm's operand form (see _text_mlp_tiles).  Forward: a = the residual stream
+    x_mid -> (partial products, mean2, rstd2), ln_2 applied while the kernel stages its rows (TEXT_MLP_PAIR_LN: the LayerNorm launch
+    in front of it goes as well) or by that launch; backward: a = the branch's output gradient -> the partial products."""
+    w1t, w2t = _text_mlp_tiles(sd, p, wcm, backward)
+    if backward:
+        return ops.text_mlp_pair(a, w1t, w2t, pre=pre, backward=True)
+    if TEXT_MLP_PAIR_LN:
+        return ops.text_mlp_pair(a, w1t, w2t, bias=sd[p + "mlp.c_fc.bias"], pre=pre, ln=(sd[p + "ln_2.weight"], sd[p + "ln_2.bias"]),
+                                 save_stats=save)
+    h2, mean2, rstd2 = ops.layernorm_fwd(a, sd[p + "ln_2.weight"], sd[p + "ln_2.bias"], wcm.dtype, save_stats=save)
+    return ops.text_mlp_pair(h2, w1t, w2t, bias=sd[p + "mlp.c_fc.bias"], pre=pre), mean2, rstd2
 
 
 def text_tower_forward(sd, wc, prompts, eot_pos, heads, layers, save, eff_len=None, prefix=0, rows_in=None):
@@ -1042,20 +1053,7 @@ def text_tower_forward(sd, wc, prompts, eot_pos, heads, layers, save, eff_len=No
         if pair:
             # c_fc + QuickGELU + c_proj in one launch; its eight partial products are this layer's output once the next layer's
             # LayerNorm has added them to x_mid and the bias (the split-K hand-over below, with 8 slices instead of 4)
-            w1t, w2t = _text_mlp_tiles(sd, p, wcm, False)
-            if Tm == torch.float32 and TEXT_MLP_PAIR_LN:
-                parts, mean2, rstd2 = ops.text_mlp_pair_split(x_mid, w1t, w2t, bias=sd[p + "mlp.c_fc.bias"], pre=pre,
-                                                              ln=(sd[p + "ln_2.weight"], sd[p + "ln_2.bias"]), save_stats=save)
-            elif Tm == torch.float32:
-                h2, mean2, rstd2 = ops.layernorm_fwd(x_mid, sd[p + "ln_2.weight"], sd[p + "ln_2.bias"], Tm, save_stats=save)
-                parts = ops.text_mlp_pair_split(h2, w1t, w2t, bias=sd[p + "mlp.c_fc.bias"], pre=pre)
-            elif TEXT_MLP_PAIR_LN:
-                # ... and ln_2 is applied while the kernel stages its rows: the LayerNorm launch in front of it goes as well
-                parts, mean2, rstd2 = ops.text_mlp_pair(x_mid, w1t, w2t, bias=sd[p + "mlp.c_fc.bias"], pre=pre,
-                                                        ln=(sd[p + "ln_2.weight"], sd[p + "ln_2.bias"]), save_stats=save)
-            else:
-                h2, mean2, rstd2 = ops.layernorm_fwd(x_mid, sd[p + "ln_2.weight"], sd[p + "ln_2.bias"], Tm, save_stats=save)
-                parts = ops.text_mlp_pair(h2, w1t, w2t, bias=sd[p + "mlp.c_fc.bias"], pre=pre)
+            parts, mean2, rstd2 = _text_mlp(x_mid, sd, p, wcm, pre=pre, save=save)
             if save:
                 saved["layers"].append(dict(x=x, mean1=mean1, rstd1=rstd1, qkv=qkv, a=a, lse=lse, x_mid=x_mid, mean2=mean2,
                                             rstd2=rstd2, pre=pre))
@@ -1142,9 +1140,7 @@ def text_tower_backward(sd, wc, s, dout, grad_scale=1.0):
         if TEXT_MLP_PAIR and splitk and _text_mlp_pair_ok(Tm) and tuple(sd[p + "mlp.c_fc.weight"].shape) == (2048, 512):
             # the branch's input gradient ((g W_proj) * QuickGELU'(pre)) W_fc in one launch: eight partial products, added up by the
             # LayerNorm backward that reads them
-            w1t, w2t = _text_mlp_tiles(sd, p, wcm, True)
-            pair_fn = ops.text_mlp_pair_split if Tm == torch.float32 else ops.text_mlp_pair
-            _, g_t = ops.layernorm_bwd_sum(pair_fn(g_t, w1t, w2t, pre=ly["pre"], backward=True), ly["x_mid"],
+            _, g_t = ops.layernorm_bwd_sum(_text_mlp(g_t, sd, p, wcm, pre=ly["pre"], backward=True), ly["x_mid"],
                                            sd[p + "ln_2.weight"], ly["mean2"], ly["rstd2"], g, accumulate=True, copy_dtype=Ta)
             d_pre = None
         else:

@@ -413,22 +413,17 @@ def lnlin(x, wt, ln, *, bias=None, ln_eps=1e-5, out=None):
     return out
 
 
-def text_mlp_retile(w1, w2):
-    """(w1 [2048, 512], w2 [512, 2048]) 16-bit row-major -> the fragment-ordered copies ppt_text_mlp_pair reads.  Forward:
-    (c_fc.weight, c_proj.weight); backward: (c_proj.weight^T, c_fc.weight^T) -- the same shapes."""
-    assert w1.dtype in HALF and w2.dtype == w1.dtype and tuple(w1.shape) == (2048, 512) and tuple(w2.shape) == (512, 2048)
+def text_mlp_retile(w1, w2, b_pow2=None):
+    """(w1 [2048, 512], w2 [512, 2048]) row-major -> the fragment-ordered copies ppt_text_mlp_pair reads (csrc/text_mlp.hip).  Forward:
+    (c_fc.weight, c_proj.weight); backward: (c_proj.weight^T, c_fc.weight^T) -- the same shapes.  16-bit weights: copies of the same
+    dtype; fp32 weights: the split16 form's hi + lo half copies (uint8 [4 MB] each), multiplied by 2^b_pow2 (default: the current
+    SPLIT16_POW2's B scale) -- the copies remember the scale they were made with (`.ppt_b_pow2`)."""
+    assert w1.dtype in HALF + (torch.float32,) and w2.dtype == w1.dtype and tuple(w1.shape) == (2048, 512) and tuple(w2.shape) == (512, 2048)
     _chk(w1, w1.dtype, "w1"); _chk(w2, w1.dtype, "w2")
-    w1t, w2t = torch.empty_like(w1), torch.empty_like(w2)
-    _lib.check(_lib.lib().ppt_text_mlp_retile(_p(w1), _p(w2), _p(w1t), _p(w2t), _stream()), "ppt_text_mlp_retile")
-    return w1t, w2t
-
-
-def text_mlp_retile_split(w1, w2, b_pow2=None):
-    """(w1 [2048, 512], w2 [512, 2048]) fp32 row-major -> the fragment-ordered hi + lo half copies (uint8 [4 MB] each) of the split16
-    form of ppt_text_mlp_pair (csrc/text_mlp_split.hip), multiplied by 2^b_pow2 (default: the current SPLIT16_POW2's B scale).  The
-    copies remember the scale they were made with (`.ppt_b_pow2`)."""
-    assert w1.dtype == torch.float32 and w2.dtype == torch.float32 and tuple(w1.shape) == (2048, 512) and tuple(w2.shape) == (512, 2048)
-    _chk(w1, torch.float32, "w1"); _chk(w2, torch.float32, "w2")
+    if w1.dtype != torch.float32:
+        w1t, w2t = torch.empty_like(w1), torch.empty_like(w2)
+        _lib.check(_lib.lib().ppt_text_mlp_retile(_p(w1), _p(w2), _p(w1t), _p(w2t), _stream()), "ppt_text_mlp_retile")
+        return w1t, w2t
     b = SPLIT16_POW2[1] if b_pow2 is None else int(b_pow2)
     w1t = torch.empty((2048 * 512 * 4,), dtype=torch.uint8, device=w1.device)
     w2t = torch.empty((2048 * 512 * 4,), dtype=torch.uint8, device=w1.device)
@@ -437,35 +432,7 @@ def text_mlp_retile_split(w1, w2, b_pow2=None):
     return w1t, w2t
 
 
-def text_mlp_pair_split(a, w1t, w2t, *, bias=None, pre=None, backward=False, a_pow2=None, ln=None, ln_eps=1e-5, save_stats=False):
-    """text_mlp_pair on fp32 operands multiplied as hi + lo half pairs (split16; csrc/text_mlp_split.hip): a [M, 512] f32, w1t / w2t
-    from text_mlp_retile_split, pre [M, 2048] f32 -> the eight slices' partial products [8, M, 512] f32."""
-    M = a.shape[0]
-    assert a.dim() == 2 and a.shape[1] == 512 and a.stride(1) == 1 and a.dtype == torch.float32 and w1t.dtype == torch.uint8
-    parts = torch.empty((8, M, 512), dtype=torch.float32, device=a.device)
-    p = _lib.TextMlpParams()
-    p.A, p.lda, p.W1, p.W2, p.b1, p.pre, p.parts = _p(a), a.stride(0), _p(w1t), _p(w2t), _p(bias), _p(pre), _p(parts)
-    p.M, p.D, p.hidden, p.mode, p.dtype = M, 512, 2048, int(bool(backward)), PPT_F32
-    p.split_a_pow2 = SPLIT16_POW2[0] if a_pow2 is None else int(a_pow2)
-    p.split_b_pow2 = int(w1t.ppt_b_pow2)
-    if not torch.cuda.is_current_stream_capturing() or a.device.index in _SPLIT_OVERFLOW:
-        p.split_overflow = _p(split16_overflow_counter(a.device))
-    if pre is not None:
-        assert pre.dtype == torch.float32 and tuple(pre.shape) == (M, 2048) and pre.is_contiguous()
-    mean = rstd = None
-    if ln is not None:              # (forward: `a` is the residual stream, ln_2 applied while the rows are staged; -> (parts, mean, rstd))
-        assert not backward
-        _chk(ln[0], torch.float32, "ln weight"); _chk(ln[1], torch.float32, "ln bias")
-        if save_stats:
-            mean = torch.empty((M,), dtype=torch.float32, device=a.device)
-            rstd = torch.empty((M,), dtype=torch.float32, device=a.device)
-        p.ln_w, p.ln_b, p.ln_eps, p.ln_mean, p.ln_rstd = _p(ln[0]), _p(ln[1]), float(ln_eps), _p(mean), _p(rstd)
-    if profiler is not None:
-        profiler.begin("gemm_f32", 4.0 * M * 512 * 2048, "ppt_text_mlp_pair split16 (" + ("backward" if backward else "forward") + ")")
-    _lib.check(_lib.lib().ppt_text_mlp_pair(ctypes.byref(p), _stream()), "ppt_text_mlp_pair (split16)")
-    if profiler is not None:
-        profiler.end()
-    return (parts, mean, rstd) if ln is not None else parts
+text_mlp_retile_split = text_mlp_retile       # (the split16 form's earlier names: the form follows the operands)
 
 
 def text_lin_retile_split(w, b_pow2=None):
@@ -482,7 +449,7 @@ def text_lin_retile_split(w, b_pow2=None):
 
 
 def text_lin_split(a, wt, *, bias=None, residual=None, out=None, a_pow2=None):
-    """a [M, K] fp32 @ W^T (+ bias) (+ residual) on split16 products, rows stationary (csrc/text_lin_split.hip; wt =
+    """a [M, K] fp32 @ W^T (+ bias) (+ residual) on split16 products, rows stationary (csrc/text_lin.hip; wt =
     text_lin_retile_split(W)) -> out [M, N] fp32; K > 512: the K / 512 partial products [K / 512, M, N] (no bias / residual)."""
     N, K = wt.ppt_shape
     M = a.shape[0]
@@ -525,7 +492,7 @@ def text_lin_retile16(w):
 
 
 def text_lin16(a, wt, *, bias=None, residual=None, out=None, out_dtype=None):
-    """a [M, K] 16-bit @ W^T (+ bias) (+ residual), rows stationary (csrc/text_lin_split.hip; wt = text_lin_retile16(W), W in a's
+    """a [M, K] 16-bit @ W^T (+ bias) (+ residual), rows stationary (csrc/text_lin.hip; wt = text_lin_retile16(W), W in a's
     dtype) -> out [M, N] in out_dtype (a's dtype by default, or fp32; out= may be a strided view); K > 512: the K / 512 fp32 partial
     products [K / 512, M, N] (no bias / residual).  16-bit results are rounded as gemm rounds them."""
     N, K = wt.ppt_shape
@@ -553,23 +520,29 @@ def text_lin16(a, wt, *, bias=None, residual=None, out=None, out_dtype=None):
     return out
 
 
-def text_mlp_pair(a, w1t, w2t, *, bias=None, pre=None, backward=False, ln=None, ln_eps=1e-5, save_stats=False):
+def text_mlp_pair(a, w1t, w2t, *, bias=None, pre=None, backward=False, a_pow2=None, ln=None, ln_eps=1e-5, save_stats=False):
     """The MLP half of a CLIP text layer in one launch (csrc/text_mlp.hip) -> the eight slices' partial products [8, M, 512] f32.
-    forward: QuickGELU(a w1^T + bias) w2^T, `pre` (optional, [M, 2048] 16-bit) receives the pre-activation; backward=True:
+    forward: QuickGELU(a w1^T + bias) w2^T, `pre` (optional, [M, 2048]) receives the pre-activation; backward=True:
     ((a w1^T) * QuickGELU'(pre)) w2^T with w1 / w2 the transposed weights' tiled copies.  The caller's LayerNorm sums the slices
-    (layernorm_fwd_sum / layernorm_bwd_sum).
+    (layernorm_fwd_sum / layernorm_bwd_sum).  The operand form follows the tiled weights (text_mlp_retile): 16-bit copies -> `a` and
+    `pre` in their dtype; the split16 copies (uint8) -> `a` and `pre` fp32, every product on hi + lo half pairs with `a` multiplied by
+    2^a_pow2 (default: the current SPLIT16_POW2's A scale).
     ln = (weight, bias) (forward only): `a` is the FP32 residual stream and the LayerNorm in front of the branch (ln_2) is applied while
     the rows are staged; save_stats -> also returns (mean, rstd) [M] for the LayerNorm backward: (parts, mean, rstd)."""
     M = a.shape[0]
-    assert a.dim() == 2 and a.shape[1] == 512 and a.stride(1) == 1 and w1t.dtype in HALF and w2t.dtype == w1t.dtype
-    if ln is None:
-        assert a.dtype == w1t.dtype
-    else:
-        assert a.dtype == torch.float32 and not backward
+    split = w1t.dtype == torch.uint8
+    t = torch.float32 if split else w1t.dtype
+    assert a.dim() == 2 and a.shape[1] == 512 and a.stride(1) == 1 and (split or t in HALF) and w2t.dtype == w1t.dtype
+    assert a.dtype == (torch.float32 if ln is not None else t) and not (ln is not None and backward)
     parts = torch.empty((8, M, 512), dtype=torch.float32, device=a.device)
     p = _lib.TextMlpParams()
     p.A, p.lda, p.W1, p.W2, p.b1, p.pre, p.parts = _p(a), a.stride(0), _p(w1t), _p(w2t), _p(bias), _p(pre), _p(parts)
-    p.M, p.D, p.hidden, p.mode, p.dtype = M, 512, 2048, int(bool(backward)), dtype_code(w1t)
+    p.M, p.D, p.hidden, p.mode, p.dtype = M, 512, 2048, int(bool(backward)), (PPT_F32 if split else dtype_code(w1t))
+    if split:
+        p.split_a_pow2 = SPLIT16_POW2[0] if a_pow2 is None else int(a_pow2)
+        p.split_b_pow2 = int(w1t.ppt_b_pow2)
+        if not torch.cuda.is_current_stream_capturing() or a.device.index in _SPLIT_OVERFLOW:
+            p.split_overflow = _p(split16_overflow_counter(a.device))
     mean = rstd = None
     if ln is not None:
         _chk(ln[0], torch.float32, "ln weight"); _chk(ln[1], torch.float32, "ln bias")
@@ -578,13 +551,17 @@ def text_mlp_pair(a, w1t, w2t, *, bias=None, pre=None, backward=False, ln=None, 
             rstd = torch.empty((M,), dtype=torch.float32, device=a.device)
         p.ln_w, p.ln_b, p.ln_eps, p.ln_mean, p.ln_rstd = _p(ln[0]), _p(ln[1]), float(ln_eps), _p(mean), _p(rstd)
     if pre is not None:
-        assert pre.dtype == w1t.dtype and tuple(pre.shape) == (M, 2048) and pre.is_contiguous()
+        assert pre.dtype == t and tuple(pre.shape) == (M, 2048) and pre.is_contiguous()
+    direction = "backward" if backward else "forward"
     if profiler is not None:
-        profiler.begin("gemm_bf16", 4.0 * M * 512 * 2048, "ppt_text_mlp_pair (" + ("backward" if backward else "forward") + ")")
-    _lib.check(_lib.lib().ppt_text_mlp_pair(ctypes.byref(p), _stream()), "ppt_text_mlp_pair")
+        profiler.begin("gemm_f32" if split else "gemm_bf16", 4.0 * M * 512 * 2048, f"ppt_text_mlp_pair {'split16 ' if split else ''}({direction})")
+    _lib.check(_lib.lib().ppt_text_mlp_pair(ctypes.byref(p), _stream()), "ppt_text_mlp_pair (split16)" if split else "ppt_text_mlp_pair")
     if profiler is not None:
         profiler.end()
     return (parts, mean, rstd) if ln is not None else parts
+
+
+text_mlp_pair_split = text_mlp_pair
 
 
 def vit_proj_retile(wp):

@@ -1568,7 +1568,7 @@ def test_text_mlp_pair_matches_the_two_linears(ops, M, dtype):
 
 @pytest.mark.parametrize("M", [817, 37, 1480])
 def test_text_mlp_pair_split16_matches_fp64_and_the_split16_gemms(ops, M):
-    """The split16 form of ppt_text_mlp_pair (csrc/text_mlp_split.hip: fp32 operands multiplied as hi + lo IEEE-half pairs, the weights
+    """The split16 form of ppt_text_mlp_pair (csrc/text_mlp.hip: fp32 operands multiplied as hi + lo IEEE-half pairs, the weights
     split once by ppt_text_mlp_retile_split) against fp64 math on the fp32 operands -- fp32-GRADE bounds, forward and backward, with
     outlier channels in the activations -- and against the two split16 tile GEMMs it replaces; the saved fp32 pre-activation; ragged last
     block; bit-reproducible; a value beyond half's range is saturated and COUNTED."""
@@ -1629,7 +1629,7 @@ def test_text_mlp_pair_split16_matches_fp64_and_the_split16_gemms(ops, M):
 @pytest.mark.parametrize("M,N,K,epi", [(817, 1536, 512, "bias"), (817, 512, 512, "bias+residual"), (817, 512, 1536, "chunks"), (37, 512, 512, "plain"),
                                        (1480, 1536, 512, "bias")])
 def test_text_lin_split16_matches_fp64_and_the_split16_gemm(ops, M, N, K, epi):
-    """ppt_text_lin_split (csrc/text_lin_split.hip: a linear of the text tower's attention half on hi + lo half products, rows stationary,
+    """ppt_text_lin_split (csrc/text_lin.hip: a linear of the text tower's attention half on hi + lo half products, rows stationary,
     the weight halves streamed) against fp64 math on the fp32 operands at fp32-grade bounds and against the split16 tile GEMM: in_proj
     (bias), out_proj (bias + residual, written over a strided output), the K = 1536 input gradient as three partial products, a ragged
     block; bit-reproducible; saturation counted."""

@@ -1,4 +1,4 @@
-"""GPU: the 16-bit form of the text-lin kernel (csrc/text_lin_split.hip, ops.text_lin16): the four linears of the text tower's
+"""GPU: the 16-bit form of the text-lin kernel (csrc/text_lin.hip, ops.text_lin16): the four linears of the text tower's
 attention half on the mixed mode's 16-bit operands, rows stationary and the weight streamed.
 
 Bounds.  A product of two f16 (11 + 11 significand bits) or two bf16 values is exact in fp32, so the only error of an fp32 result is

@@ -24,7 +24,7 @@ for nm, K, N, resid in (("out_proj fwd/bwd", 512, 512, True), ("c_proj fwd", 204
     print(f"{nm:18s} M={M} K={K:4d} N={N:4d}: {t:6.1f} us ({fl / t / 1e6:5.0f} TF), min traffic {(M * K + N * K) * 2 / 1e6:.1f} MB", flush=True)
 
 # The attention half's four linears in the mixed mode's operand format (PPT_TEXT_F16: IEEE half) on the text-lin kernel
-# (csrc/text_lin_split.hip, ops.text_lin16) beside the tile GEMM the tower used before (ops.gemm / ops.gemm_splitk).
+# (csrc/text_lin.hip, ops.text_lin16) beside the tile GEMM the tower used before (ops.gemm / ops.gemm_splitk).
 for dt in (torch.float16, torch.bfloat16):
     for nm, K, N, epi in (("in_proj", 512, 1536, "bias"), ("out_proj", 512, 512, "bias+residual"), ("d out_proj", 512, 512, "plain"),
                           ("d in_proj", 1536, 512, "chunks")):

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Dev tool (round 6): the text tower's MLP half -- ppt_text_mlp_pair (one launch) against the two launches it replaces (ppt_gemm
-with the QuickGELU epilogue, then the split-K c_proj product), forward and backward, at the prompt chain's sizes.
-    python3 tools/text_mlp_bench.py"""
+with the QuickGELU epilogue, then the split-K c_proj product), forward and backward, at the prompt chain's sizes, in both operand
+forms of csrc/text_mlp.hip: IEEE half, and fp32 operands as hi + lo half pairs (split16).
+    python3 tools/text_mlp_bench.py [rows ...]"""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ppt_amd import ops
 
-dt = torch.float16
 g = torch.Generator().manual_seed(0)
 
 
@@ -24,9 +24,11 @@ def timeit(fn, iters=300):
     return 1e3 * a.elapsed_time(b) / iters
 
 
-print("| rows | direction | two launches (us) | one launch (us) |")
-print("|---|---|---|---|")
-for M in (817, 317, 1037, 3080):
+ops.set_split16(True)                     # (the fp32 tile GEMMs of the two-launch baseline run on split16 products too)
+print("| operands | rows | direction | two launches (us) | one launch (us) |")
+print("|---|---|---|---|---|")
+for dt, M in [(dt, M) for dt in (torch.float16, torch.float32) for M in ([int(x) for x in sys.argv[1:]] or (817, 317, 1037, 3080))]:
+    form = "split16" if dt == torch.float32 else "f16"
     a = torch.randn(M, 512, generator=g).cuda().to(dt)
     w1 = (torch.randn(2048, 512, generator=g) * 512 ** -0.5).cuda().to(dt)
     w2 = (torch.randn(512, 2048, generator=g) * 2048 ** -0.5).cuda().to(dt)
@@ -45,5 +47,5 @@ for M in (817, 317, 1037, 3080):
         return ops.gemm_splitk(d_pre, w1T, 4)
     t2f, t1f = timeit(two_fwd), timeit(lambda: ops.text_mlp_pair(a, w1t, w2t, bias=b1, pre=pre))
     t2b, t1b = timeit(two_bwd), timeit(lambda: ops.text_mlp_pair(a, b1t, b2t, pre=pre, backward=True))
-    print(f"| {M} | forward | {t2f:.1f} | {t1f:.1f} |")
-    print(f"| {M} | backward | {t2b:.1f} | {t1b:.1f} |", flush=True)
+    print(f"| {form} | {M} | forward | {t2f:.1f} | {t1f:.1f} |")
+    print(f"| {form} | {M} | backward | {t2b:.1f} | {t1b:.1f} |", flush=True)
