@@ -431,7 +431,7 @@ int ppt_attention_bwd(const void *qkv, const void *out, const void *dout, const 
  * [C + 1, P, 2, H * hd] and a last kernel folds them in sequence order (deterministic, no atomics).
  * lse / delta: [P + C (T - P), H] f32, indexed by ROW.  0 < P < T; hd == 64; same kernels as ppt_attention_fwd / _bwd. */
 size_t ppt_attention_prefix_workspace_bytes(int C, int P, int H, int hd);
-/* split16 forward (ABI 6; csrc/attention_split.hip): fp32 qkv / out in the layouts of ppt_attention_fwd (P == 0) or
+/* split16 forward (ABI 6; csrc/attention_mfma.hip: the PPT_F32 form of attn_fwd_stream): fp32 qkv / out in the layouts of ppt_attention_fwd (P == 0) or
  * ppt_attention_prefix_fwd (P > 0, causal, C = Bt prompts), both products on the 16-bit matrix pipe from hi + lo IEEE-half pairs
  * of the fp32 operands (K.Q^T and V^T.P each as three MFMAs, fp32 accumulation; softmax statistics, rescale and output fp32):
  * the fp32 kernel's results to ~1e-6 at 4x its rate.  hd must be 64; qkv and out 16-byte aligned. */

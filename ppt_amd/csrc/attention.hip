@@ -10,19 +10,11 @@
 // staged through LDS in 32-row tiles.  They are the parity-mode (PPT_F32) implementation and the
 // general backward.  The bf16 MFMA flash forward lives in attention_mfma.hip and is dispatched from
 // here for PPT_BF16.
-#include "ppt_common.h"
-#include "attn_rowmap.h"
-
-// (fmt: PPT_BF16 or PPT_F16, the 16-bit operand format)
-extern "C" int ppt_attention_fwd_mfma_bf16(const void *qkv, void *out, float *lse, int Bt, int T, int H,
-                                           float scale, int causal, int P, int fmt, hipStream_t s);
-extern "C" int ppt_attention_bwd_mfma_bf16(const void *qkv, const void *dout, const float *lse, const float *delta,
-                                           void *dqkv, int Bt, int T, int H, float scale, int causal, int P, float *part,
-                                           int fmt, hipStream_t s);
+#include "attn_common.h"
 
 namespace {
 
-constexpr int HD = 64, SEG = 16, KT = 32, ROWS = 64;   // rows per 256-thread block
+constexpr int SEG = 16, KT = 32, ROWS = 64;   // rows per 256-thread block (HD = 64: attn_common.h)
 
 __device__ __forceinline__ float quad_sum(float v)
 {
@@ -298,11 +290,11 @@ int attn_fwd_t(const void *qkv, void *out, float *lse, int Bt, int Tl, int H, fl
 __host__ int64_t attn_rows(int Bt, int Tl, int P) { return P > 0 ? (int64_t)P + (int64_t)Bt * (Tl - P) : (int64_t)Bt * Tl; }
 
 template <typename T>
-int attn_reduce_t(const float *part, void *dqkv, int Bt, int P, int H, hipStream_t s)
+int attn_reduce_t(const float *part, void *dqkv, int Bt, int P, int H, int prio, hipStream_t s)
 {
     if (P <= 0) return PPT_OK;
     const int n = P * 2 * H * HD;
-    hipLaunchKernelGGL(attn_prefix_reduce<T>, dim3((n + 255) / 256), dim3(256), 0, s, part, Bt + 1, P, H * HD, (T *)dqkv, ppt_get_wave_priority());
+    hipLaunchKernelGGL(attn_prefix_reduce<T>, dim3((n + 255) / 256), dim3(256), 0, s, part, Bt + 1, P, H * HD, (T *)dqkv, prio);
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }
@@ -324,7 +316,7 @@ int attn_bwd_t(const void *qkv, const void *out, const void *dout, const float *
     hipLaunchKernelGGL(attn_bwd_dkv<T>, grid, dim3(256), 0, s, (const T *)qkv, (const T *)dout, lse, delta, (T *)dqkv,
                        Tl, H, scale, causal, P, Bt, part);
     PPT_CHECK_LAUNCH();
-    return attn_reduce_t<T>(part, dqkv, Bt, P, H, s);
+    return attn_reduce_t<T>(part, dqkv, Bt, P, H, ppt_get_wave_priority(), s);
 }
 
 }  // namespace
@@ -345,12 +337,16 @@ extern "C" int ppt_attention_fwd(const void *qkv, void *out, float *lse, int Bt,
 }
 
 // used by attention_mfma.hip until every shape has an MFMA kernel
-extern "C" int ppt_attention_bwd_short_mfma_bf16(const void *qkv, const void *out, const void *dout, const float *lse, void *dqkv, int Bt, int T,
-                                                 int H, float scale, int causal, int P, float *part, int fmt, hipStream_t s);
 extern "C" int ppt_attention_fwd_quad_bf16(const void *qkv, void *out, float *lse, int Bt, int T, int H, float scale,
                                            int causal, int P, int fmt, hipStream_t s)
 {
     return fmt == PPT_F16 ? attn_fwd_t<f16_t>(qkv, out, lse, Bt, T, H, scale, causal, P, s) : attn_fwd_t<bf16_t>(qkv, out, lse, Bt, T, H, scale, causal, P, s);
+}
+
+// the split16 backward's fold of its partial slots (attention_split.hip)
+extern "C" int ppt_attention_prefix_reduce_f32(const float *part, void *dqkv, int Bt, int P, int H, int prio, hipStream_t s)
+{
+    return attn_reduce_t<float>(part, dqkv, Bt, P, H, prio, s);
 }
 
 static int attn_bwd_any(const void *qkv, const void *out, const void *dout, const float *lse, float *delta, void *dqkv, float *part,
@@ -363,7 +359,8 @@ static int attn_bwd_any(const void *qkv, const void *out, const void *dout, cons
     if (dtype == PPT_BF16 || dtype == PPT_F16) {
         hipStream_t s = ppt_stream(stream);
         const bool f16 = dtype == PPT_F16;
-        auto reduce = [&]() { return f16 ? attn_reduce_t<f16_t>(part, dqkv, Bt, P, H, s) : attn_reduce_t<bf16_t>(part, dqkv, Bt, P, H, s); };
+        const int prio = ppt_get_wave_priority();
+        auto reduce = [&]() { return f16 ? attn_reduce_t<f16_t>(part, dqkv, Bt, P, H, prio, s) : attn_reduce_t<bf16_t>(part, dqkv, Bt, P, H, prio, s); };
         if (T <= 128) {                                    // short sequences (the text tower): delta + dK/dV + dQ in ONE launch
             const int rc = ppt_attention_bwd_short_mfma_bf16(qkv, out, dout, lse, dqkv, Bt, T, H, scale, causal, P, part, dtype, s);
             if (rc == PPT_OK) return reduce();

@@ -1,4 +1,5 @@
-// attention_mfma.hip -- bf16 flash-attention forward on the gfx950 matrix cores (head dim 64).
+// attention_mfma.hip -- flash attention on the gfx950 matrix cores (head dim 64): the streaming forward of the 16-bit and the
+// split16 form, the resident forward and the backward of the 16-bit form.
 //
 // Replaces point_encoder.py:46-55 (T = 513, non-causal) and nn.MultiheadAttention at
 // ULIP_models.py:38,49-51 (L = 77, causal) for the bf16 performance mode.
@@ -13,64 +14,244 @@
 //   with the hardware transpose read ds_read_b64_tr_b16; the V image XORs address bit 6 with bit 1
 //   of the key so that the four key rows of a half-wave hit four different 64-byte bank quarters.
 //   Scores never leave registers; softmax scale and log2(e) are folded into one v_exp_f32 argument.
-#include "ppt_common.h"
+//
+// The streaming kernel has two operand forms (FORM, as in csrc/text_mlp.hip):
+//   * PPT_BF16 / PPT_F16: the 16-bit q / k / v of the mixed mode as they are -- one LDS image of K and of V, one MFMA per fragment;
+//   * PPT_F32 (precision mode "split16"): fp32 q / k / v with every operand of the two products split into hi + lo IEEE-half pairs
+//     (attn_common.h: 22 significand bits, the lo x lo term dropped):
+//         S^T = K . Q^T   = K_lo.Q_hi + K_hi.Q_lo + K_hi.Q_hi          (v_mfma_f32_32x32x16_f16, fp32 accumulation)
+//         O^T = V^T . P   = V_lo.P_hi + V_hi.P_lo + V_hi.P_hi
+//     K and V are split ONCE per workgroup where the register-staged tile goes to LDS (hi and lo images of the 64-key tile, the
+//     16-bit form's swizzles); Q is split once per wave into registers; P = exp2(S c - m) in [0, 1] is split in registers on its
+//     way from the S^T accumulator layout to the B operand.  Softmax statistics, the running rescale, the peeled last key of
+//     T = 64 n + 1 and the output are fp32.  48 MFMAs per 64-key tile and wave instead of 16.  (The fp32 parity mode's VALU
+//     kernel, attention.hip: attn_fwd_quad<float>, 57 TFLOP/s at the ViT shape: 225 us per call, 5.4 of the 13.8 ms of a C2
+//     step once the GEMMs are split16.)
+// AttnForm<FORM> holds what differs; the row map, the peel, the masking, the online softmax and the tile pipeline are one text.
 #include <stdlib.h>
-#include "attn_rowmap.h"
-
-extern "C" int ppt_attention_fwd_quad_bf16(const void *qkv, void *out, float *lse, int Bt, int T, int H, float scale,
-                                           int causal, int P, int fmt, hipStream_t s);
+#include <type_traits>
+#include "attn_common.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) short s4_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
+template <int FORM> struct AttnForm {                              // the 16-bit forms
+    using F = typename std::conditional<FORM == PPT_BF16, bf16_t, f16_t>::type;
+    using T = bf16_t;                                              // element of qkv / out (raw 16 bits of either format)
+    using chunk_t = uint4;                                         // 16 staged bytes: 8 elements
+    static constexpr int IMAGES = 1, CH_SHIFT = 3;                 // LDS images per K or V tile; log2(16-byte chunks per row)
+    static constexpr float P_PRE = 1.0f;
+    // Q^T: lane (r, h) holds dimensions 16 kk + 8 h .. + 7 of its query row as raw[kk][..]; here that is the B fragment itself
+    struct Q { chunk_t raw[4][1]; };
 
-constexpr int HD = 64, KVT = 64, QB = 128, TILE = KVT * 128;   // bytes per K or V tile (64 keys x 128 B)
+    static __device__ __forceinline__ chunk_t zero() { return make_uint4(0, 0, 0, 0); }
+    static __device__ __forceinline__ void prep_q(Q &, int) {}
+    static __device__ __forceinline__ void write(unsigned char *kimg, unsigned char *vimg, int row, int ch, const chunk_t &k, const chunk_t &v)
+    {
+        *reinterpret_cast<uint4 *>(kimg + k_off(row, ch)) = k;
+        *reinterpret_cast<uint4 *>(vimg + v_off(row, ch * 16)) = v;
+    }
+    // this lane's 32 of the 64 terms of q . k_last
+    static __device__ __forceinline__ float peel_dot(const T *kl, const Q &q, int h)
+    {
+        float dot = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            const uint4 kv = *reinterpret_cast<const uint4 *>(kl + 16 * kk + 8 * h);
+            const uint4 qv = q.raw[kk][0];
+            const uint32_t kw[4] = {kv.x, kv.y, kv.z, kv.w}, qw[4] = {qv.x, qv.y, qv.z, qv.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                dot = fmaf(h16<F>::lo(kw[e]), h16<F>::lo(qw[e]), dot);
+                dot = fmaf(h16<F>::hi(kw[e]), h16<F>::hi(qw[e]), dot);
+            }
+        }
+        return dot;
+    }
+    static __device__ __forceinline__ void peel_o(const T *vl, int h, f32x16_t (&ot)[2])
+    {
+#pragma unroll
+        for (int dtile = 0; dtile < 2; ++dtile)
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const uint2 vv = *reinterpret_cast<const uint2 *>(vl + 32 * dtile + 8 * gq + 4 * h);
+                ot[dtile][4 * gq + 0] = h16<F>::lo(vv.x); ot[dtile][4 * gq + 1] = h16<F>::hi(vv.x);
+                ot[dtile][4 * gq + 2] = h16<F>::lo(vv.y); ot[dtile][4 * gq + 3] = h16<F>::hi(vv.y);
+            }
+    }
+    static __device__ __forceinline__ void qk(f32x16_t (&st)[2], const unsigned char *Kc, const Q &q, int r, int h)
+    {
+        // all eight K fragments first (independent ds_read_b128, one wait), then the MFMAs: loaded one by one, each
+        // MFMA waited for its own LDS round trip
+        uint4 kf[4][2];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) kf[kk][sub] = *reinterpret_cast<const uint4 *>(Kc + k_off(32 * sub + r, 2 * kk + h));
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) st[sub] = h16<F>::mfma32(kf[kk][sub], q.raw[kk][0], st[sub]);
+    }
+    // P (still in the S^T accumulator layout) -> B fragments of the 16-key k-steps, then O^T += V^T . P
+    static __device__ __forceinline__ void pv(f32x16_t (&ot)[2], const f32x16_t (&st)[2], const unsigned char *Vc, int tr_key, int tr_dbyte)
+    {
+        uint4 pf[2][2];
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) pf[sub][s] = pack8<F>(st[sub], s);
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int dtile = 0; dtile < 2; ++dtile)
+                    ot[dtile] = h16<F>::mfma32(tr_frag(Vc, 32 * sub + 16 * s + tr_key, tr_dbyte + 64 * dtile), pf[sub][s], ot[dtile]);
+    }
+    static __device__ __forceinline__ void store_o(T *ob, const f32x16_t (&ot)[2], float inv, int h)
+    {
+#pragma unroll
+        for (int dtile = 0; dtile < 2; ++dtile)
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const uint2 u = make_uint2(h16<F>::pack2(ot[dtile][4 * gq + 0] * inv, ot[dtile][4 * gq + 1] * inv),
+                                           h16<F>::pack2(ot[dtile][4 * gq + 2] * inv, ot[dtile][4 * gq + 3] * inv));
+                *reinterpret_cast<uint2 *>(ob + 32 * dtile + 8 * gq + 4 * h) = u;
+            }
+    }
+};
 
-__device__ __forceinline__ int k_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int v_off(int key, int dbyte) { return key * 128 + (dbyte ^ (((key >> 1) & 1) << 6)); }
+template <> struct AttnForm<PPT_F32> {                             // split16: the same members over hi + lo half pairs
+    using T = float;
+    using chunk_t = float4;                                        // 16 staged bytes: 4 elements
+    static constexpr int IMAGES = 2, CH_SHIFT = 4;
+    static constexpr float P_PRE = 1024.0f;                        // P is split as P x 2^10, O carries the factor to the end
+    struct Q { chunk_t raw[4][2]; uint4 h[4], l[4]; };             // the fp32 values (for the peel) and their hi and lo halves
 
-// (ppt_common.h: v_permlane32_swap with wait states on both sides)
-__device__ __forceinline__ float lane_xor32_max(float v) { return xor32_max(v); }
-__device__ __forceinline__ float lane_xor32_sum(float v) { return xor32_sum(v); }
+    static __device__ __forceinline__ chunk_t zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+    static __device__ __forceinline__ void prep_q(Q &q, int kk) { split8(q.raw[kk][0], q.raw[kk][1], q.h[kk], q.l[kk]); }
+    // the split: 4 floats -> 8 bytes of the hi image + 8 of the lo image
+    static __device__ __forceinline__ void write(unsigned char *kimg, unsigned char *vimg, int row, int ch, const chunk_t &k, const chunk_t &v)
+    {
+        uint2 hi, lo;
+        split2(k.x, k.y, hi.x, lo.x); split2(k.z, k.w, hi.y, lo.y);
+        const int ko = k_off(row, ch >> 1) + (ch & 1) * 8;
+        *reinterpret_cast<uint2 *>(kimg + ko) = hi;
+        *reinterpret_cast<uint2 *>(kimg + TILE + ko) = lo;
+        split2(v.x, v.y, hi.x, lo.x); split2(v.z, v.w, hi.y, lo.y);
+        const int vo = v_off(row, ch * 8);
+        *reinterpret_cast<uint2 *>(vimg + vo) = hi;
+        *reinterpret_cast<uint2 *>(vimg + TILE + vo) = lo;
+    }
+    static __device__ __forceinline__ float peel_dot(const T *kl, const Q &q, int h)      // fp32 throughout
+    {
+        float dot = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            const float4 k0 = *reinterpret_cast<const float4 *>(kl + 16 * kk + 8 * h);
+            const float4 k1 = *reinterpret_cast<const float4 *>(kl + 16 * kk + 8 * h + 4);
+            dot = fmaf(k0.x, q.raw[kk][0].x, dot); dot = fmaf(k0.y, q.raw[kk][0].y, dot);
+            dot = fmaf(k0.z, q.raw[kk][0].z, dot); dot = fmaf(k0.w, q.raw[kk][0].w, dot);
+            dot = fmaf(k1.x, q.raw[kk][1].x, dot); dot = fmaf(k1.y, q.raw[kk][1].y, dot);
+            dot = fmaf(k1.z, q.raw[kk][1].z, dot); dot = fmaf(k1.w, q.raw[kk][1].w, dot);
+        }
+        return dot;
+    }
+    static __device__ __forceinline__ void peel_o(const T *vl, int h, f32x16_t (&ot)[2])
+    {
+#pragma unroll
+        for (int dtile = 0; dtile < 2; ++dtile)
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const float4 vv = *reinterpret_cast<const float4 *>(vl + 32 * dtile + 8 * gq + 4 * h);
+                ot[dtile][4 * gq + 0] = vv.x * P_PRE; ot[dtile][4 * gq + 1] = vv.y * P_PRE;
+                ot[dtile][4 * gq + 2] = vv.z * P_PRE; ot[dtile][4 * gq + 3] = vv.w * P_PRE;
+            }
+    }
+    static __device__ __forceinline__ void qk(f32x16_t (&st)[2], const unsigned char *Kh, const Q &q, int r, int h)
+    {
+        const unsigned char *Kl = Kh + TILE;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            uint4 kh[2], kl[2];
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+                const int o = k_off(32 * sub + r, 2 * kk + h);
+                kh[sub] = *reinterpret_cast<const uint4 *>(Kh + o);
+                kl[sub] = *reinterpret_cast<const uint4 *>(Kl + o);
+            }
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) st[sub] = mfma3(kh[sub], kl[sub], q.h[kk], q.l[kk], st[sub]);
+        }
+    }
+    static __device__ __forceinline__ void pv(f32x16_t (&ot)[2], const f32x16_t (&st)[2], const unsigned char *Vh, int tr_key, int tr_dbyte)
+    {
+        const unsigned char *Vl = Vh + TILE;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                uint4 ph, pl;
+                split_acc(st[sub], s, ph, pl);
+#pragma unroll
+                for (int dtile = 0; dtile < 2; ++dtile) {
+                    const uint4 vh = tr_frag(Vh, 32 * sub + 16 * s + tr_key, tr_dbyte + 64 * dtile);
+                    const uint4 vl = tr_frag(Vl, 32 * sub + 16 * s + tr_key, tr_dbyte + 64 * dtile);
+                    ot[dtile] = mfma3(vh, vl, ph, pl, ot[dtile]);
+                }
+            }
+    }
+    static __device__ __forceinline__ void store_o(T *ob, const f32x16_t (&ot)[2], float inv, int h)
+    {
+#pragma unroll
+        for (int dtile = 0; dtile < 2; ++dtile)
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq)
+                *reinterpret_cast<float4 *>(ob + 32 * dtile + 8 * gq + 4 * h) =
+                    make_float4(ot[dtile][4 * gq + 0] * inv, ot[dtile][4 * gq + 1] * inv, ot[dtile][4 * gq + 2] * inv, ot[dtile][4 * gq + 3] * inv);
+    }
+};
 
-// Workgroup -> (query block, batch x head): the dispatcher deals consecutive workgroups round-robin to the 8 XCDs, each with an
-// L2 of its own.  With the query blocks of one (batch, head) on consecutive workgroup ids its K / V rows were fetched from HBM
-// by up to five XCDs (PMC: 139 MB read per launch at T = 513, B = 32 for 38 MB of qkv).  When the number of (batch, head)
-// pairs is a multiple of 8 the ids are dealt so that all query blocks of a pair land on ONE XCD, next to each other in time.
-// (Tried: T = 4 x 128 + 1 as four blocks of FIVE waves, the fifth wave of the last block owning the class-token row, instead of
-// a fifth block that streams every K / V tile for one row: 36.3 -> 49.0 us.  Five-wave workgroups fit three to a CU instead of
-// five, and this kernel lives on occupancy.  The ViT shape has a kernel of its own: attn_fwd_resident below.)
-template <bool CAUSAL, typename F>
-__global__ __launch_bounds__(256, 2) void attn_fwd_mfma(const bf16_t *__restrict__ qkv, bf16_t *__restrict__ out,
-                                                     float *__restrict__ lse, int Tfull, int H, float c /* scale*log2(e) */,
-                                                     int P, int C, int prio, int xcd_map)
+// (Tried for the XCD block map of attn_common.h: T = 4 x 128 + 1 as four blocks of FIVE waves, the fifth wave of the last block
+// owning the class-token row, instead of a fifth block that streams every K / V tile for one row: 36.3 -> 49.0 us.  Five-wave
+// workgroups fit three to a CU instead of five, and this kernel lives on occupancy.  The ViT shape has a kernel of its own:
+// attn_fwd_resident below.)
+template <int FORM, bool CAUSAL>
+__global__ __launch_bounds__(256, 2) void attn_fwd_stream(const typename AttnForm<FORM>::T *__restrict__ qkv,
+                                                       typename AttnForm<FORM>::T *__restrict__ out, float *__restrict__ lse, int Tfull,
+                                                       int H, float c /* scale*log2(e) */, int P, int C, int prio, int xcd_map)
 {
-    __shared__ __align__(16) unsigned char smem[4 * TILE];    // K0 K1 V0 V1
+    using A = AttnForm<FORM>;
+    using E = typename A::T;
+    constexpr int IMG = A::IMAGES * TILE;                      // bytes of a K or V tile in LDS
+    __shared__ __align__(16) unsigned char smem[2 * A::IMAGES * 2 * TILE];    // K0 K1 V0 V1, each its IMAGES images
     PPT_PRIO(prio);
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 31, h = lane >> 5;
-    int bh = blockIdx.y, qblk = blockIdx.x;
-    if (xcd_map && (gridDim.y & 7) == 0) {
-        const int lin = blockIdx.y * gridDim.x + blockIdx.x, slot = lin >> 3;
-        bh = (slot / (int)gridDim.x) * 8 + (lin & 7);
-        qblk = slot % (int)gridDim.x;
-    }
+    int bh, qblk;
+    attn_xcd_map(xcd_map, qblk, bh);
     const int b = bh / H, head = bh % H;
     const int64_t rs = 3 * (int64_t)H * HD;
     const int T = am_len(Tfull, P, C, b), q_lo = am_qlo(P, C, b);     // (attn_rowmap.h: b is a virtual sequence when P > 0)
-    const bf16_t *qb = qkv + head * HD;
-    const bf16_t *kb = qb + H * HD, *vb = qb + 2 * H * HD;
+    const E *qb = qkv + head * HD;
+    const E *kb = qb + H * HD, *vb = qb + 2 * H * HD;
     const int q0 = qblk * QB + w * 32;
     const int qrow = q0 + r;
 
-    uint4 qf[4];
+    using chunk_t = typename A::chunk_t;
+    constexpr int EPC = 16 / (int)sizeof(E);                   // elements per 16-byte chunk
+    typename A::Q q;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (qrow < T) v = *reinterpret_cast<const uint4 *>(qb + am_row(Tfull, P, b, qrow) * rs + 16 * kk + 8 * h);
-        qf[kk] = (v);
+#pragma unroll
+        for (int j = 0; j < 8 / EPC; ++j) q.raw[kk][j] = A::zero();
+        if (qrow < T) {
+            const E *qp = qb + am_row(Tfull, P, b, qrow) * rs + 16 * kk + 8 * h;
+#pragma unroll
+            for (int j = 0; j < 8 / EPC; ++j) q.raw[kk][j] = *reinterpret_cast<const chunk_t *>(qp + EPC * j);
+        }
+        A::prep_q(q, kk);
     }
 
     // T = 64 n + 1 (the ViT's class token: 513): the last key would cost a ninth 64-key tile for ONE key.  It is peeled:
@@ -78,27 +259,26 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_mfma(const bf16_t *__restrict
     // the remaining 64 n keys in whole, unmasked tiles.  (Same softmax, another summation order.)
     const bool peel = !CAUSAL && T > KVT && (T % KVT) == 1;
     const int Tk = peel ? T - 1 : T;
-    uint4 sk[2], sv[2];
+    constexpr int NST = (KVT << A::CH_SHIFT) / 256;            // 16-byte chunks of a K (or V) tile per thread
+    chunk_t sk[NST], sv[NST];                                  // the next tile, register-staged
     auto load_tile = [&](int kt) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < NST; ++i) {
             const int cidx = threadIdx.x + 256 * i;
-            const int key = kt * KVT + (cidx >> 3), ch = cidx & 7;
-            sk[i] = sv[i] = make_uint4(0, 0, 0, 0);
+            const int key = kt * KVT + (cidx >> A::CH_SHIFT), ch = cidx & ((1 << A::CH_SHIFT) - 1);
+            sk[i] = sv[i] = A::zero();
             if (key < Tk) {
                 const int64_t kr = am_row(Tfull, P, b, key) * rs;
-                sk[i] = *reinterpret_cast<const uint4 *>(kb + kr + ch * 8);
-                sv[i] = *reinterpret_cast<const uint4 *>(vb + kr + ch * 8);
+                sk[i] = *reinterpret_cast<const chunk_t *>(kb + kr + ch * EPC);
+                sv[i] = *reinterpret_cast<const chunk_t *>(vb + kr + ch * EPC);
             }
         }
     };
     auto write_tile = [&](int buf) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < NST; ++i) {
             const int cidx = threadIdx.x + 256 * i;
-            const int row = cidx >> 3, ch = cidx & 7;
-            *reinterpret_cast<uint4 *>(smem + buf * TILE + k_off(row, ch)) = sk[i];
-            *reinterpret_cast<uint4 *>(smem + (2 + buf) * TILE + v_off(row, ch * 16)) = sv[i];
+            A::write(smem + buf * IMG, smem + (2 + buf) * IMG, cidx >> A::CH_SHIFT, cidx & ((1 << A::CH_SHIFT) - 1), sk[i], sv[i]);
         }
     };
 
@@ -112,29 +292,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_mfma(const bf16_t *__restrict
         for (int e = 0; e < 16; ++e) ot[i][e] = 0.f;
     float m = -INFINITY, l = 0.f;
     if (peel) {
-        const bf16_t *kl = kb + am_row(Tfull, P, b, T - 1) * rs, *vl = vb + am_row(Tfull, P, b, T - 1) * rs;
-        float dot = 0.f;                                  // this lane's 32 of the 64 dimensions; the other half-wave has the rest
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const uint4 kv = *reinterpret_cast<const uint4 *>(kl + 16 * kk + 8 * h);
-            const uint4 qv = (qf[kk]);
-            const uint32_t kw[4] = {kv.x, kv.y, kv.z, kv.w}, qw[4] = {qv.x, qv.y, qv.z, qv.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                dot = fmaf(h16<F>::lo(kw[e]), h16<F>::lo(qw[e]), dot);
-                dot = fmaf(h16<F>::hi(kw[e]), h16<F>::hi(qw[e]), dot);
-            }
-        }
-        m = lane_xor32_sum(dot) * c;
+        const E *kl = kb + am_row(Tfull, P, b, T - 1) * rs, *vl = vb + am_row(Tfull, P, b, T - 1) * rs;
+        m = xor32_sum(A::peel_dot(kl, q, h)) * c;         // (the other half-wave has the other 32 dimensions)
         l = h == 0 ? 1.0f : 0.0f;                         // (the two half-waves' sums are added at the end)
-#pragma unroll
-        for (int dtile = 0; dtile < 2; ++dtile)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const uint2 vv = *reinterpret_cast<const uint2 *>(vl + 32 * dtile + 8 * gq + 4 * h);
-                ot[dtile][4 * gq + 0] = h16<F>::lo(vv.x); ot[dtile][4 * gq + 1] = h16<F>::hi(vv.x);
-                ot[dtile][4 * gq + 2] = h16<F>::lo(vv.y); ot[dtile][4 * gq + 3] = h16<F>::hi(vv.y);
-            }
+        A::peel_o(vl, h, ot);
     }
 
     // per-lane constant part of the transposed V reads: lane = 16g + 4q + p supplies row q, columns 4p..4p+3
@@ -150,27 +311,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_mfma(const bf16_t *__restrict
         if (kt + 1 < nkt) load_tile(kt + 1);
         const bool active = q0 < T && (!CAUSAL || kt * KVT <= q0 + 31);      // wave-uniform
         if (active) {
-            const unsigned char *Kc = smem + cur * TILE;
-            const unsigned char *Vc = smem + (2 + cur) * TILE;
+            const unsigned char *Kc = smem + cur * IMG, *Vc = smem + (2 + cur) * IMG;
             f32x16_t st[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) st[i][e] = 0.f;
-            // all eight K fragments first (independent ds_read_b128, one wait), then the MFMAs: loaded one by one, each
-            // MFMA waited for its own LDS round trip
-            uint4 kf[4][2];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub)
-                    kf[kk][sub] = __builtin_bit_cast(
-                        uint4, *reinterpret_cast<const uint4 *>(Kc + k_off(32 * sub + r, 2 * kk + h)));
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub)
-                    st[sub] = h16<F>::mfma32(kf[kk][sub], qf[kk], st[sub]);
+            A::qk(st, Kc, q, r, h);
             const bool need_mask = (kt * KVT + KVT > Tk) || (CAUSAL && kt * KVT + KVT - 1 > q0);
             if (need_mask) {
 #pragma unroll
@@ -186,7 +333,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_mfma(const bf16_t *__restrict
             for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) mx = fmaxf(mx, st[sub][e]);
-            mx = lane_xor32_max(mx);
+            mx = xor32_max(mx);
             const float mn = fmaxf(m, mx * c);
             const float alpha = __builtin_amdgcn_exp2f(m - mn);
             m = mn;
@@ -196,7 +343,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_mfma(const bf16_t *__restrict
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const float pv = __builtin_amdgcn_exp2f(fmaf(st[sub][e], c, -mn));
-                    st[sub][e] = pv;
+                    if constexpr (A::P_PRE != 1.0f) st[sub][e] = pv * A::P_PRE;      // (P <= 1: x 2^10 keeps a flat softmax's 1 / T inside hi + lo's 22 bits)
+                    else st[sub][e] = pv;
                     psum += pv;
                 }
             l = fmaf(l, alpha, psum);
@@ -204,50 +352,18 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_mfma(const bf16_t *__restrict
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) ot[i][e] *= alpha;
-            // P (still in the S^T accumulator layout) -> bf16 B fragments of the 16-key k-steps
-            uint4 pf[2][2];
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const uint4 u = make_uint4(h16<F>::pack2(st[sub][8 * s + 0], st[sub][8 * s + 1]),
-                                               h16<F>::pack2(st[sub][8 * s + 2], st[sub][8 * s + 3]),
-                                               h16<F>::pack2(st[sub][8 * s + 4], st[sub][8 * s + 5]),
-                                               h16<F>::pack2(st[sub][8 * s + 6], st[sub][8 * s + 7]));
-                    pf[sub][s] = (u);
-                }
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int dtile = 0; dtile < 2; ++dtile) {
-                        const int key0 = 32 * sub + 16 * s + tr_key;
-                        struct { s4_t a, b; } vf;
-                        vf.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (__attribute__((address_space(3))) s4_t *)(Vc + v_off(key0, tr_dbyte + 64 * dtile)));
-                        vf.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (__attribute__((address_space(3))) s4_t *)(Vc + v_off(key0 + 8, tr_dbyte + 64 * dtile)));
-                        ot[dtile] = h16<F>::mfma32(__builtin_bit_cast(uint4, vf), pf[sub][s],
-                                                                             ot[dtile]);
-                    }
+            A::pv(ot, st, Vc, tr_key, tr_dbyte);
         }
         if (kt + 1 < nkt) write_tile(cur ^ 1);
         __syncthreads();
     }
 
-    const float lt = lane_xor32_sum(l);
+    const float lt = xor32_sum(l);
     if (qrow < T && qrow >= q_lo) {
-        const float inv = 1.0f / lt;
-        bf16_t *ob = out + am_row(Tfull, P, b, qrow) * (H * HD) + head * HD;
-#pragma unroll
-        for (int dtile = 0; dtile < 2; ++dtile)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const uint2 u = make_uint2(h16<F>::pack2(ot[dtile][4 * gq + 0] * inv, ot[dtile][4 * gq + 1] * inv),
-                                           h16<F>::pack2(ot[dtile][4 * gq + 2] * inv, ot[dtile][4 * gq + 3] * inv));
-                *reinterpret_cast<uint2 *>(ob + 32 * dtile + 8 * gq + 4 * h) = u;
-            }
+        float inv;
+        if constexpr (A::P_PRE != 1.0f) inv = 1.0f / (lt * A::P_PRE);
+        else inv = 1.0f / lt;
+        A::store_o(out + am_row(Tfull, P, b, qrow) * (H * HD) + head * HD, ot, inv, h);
         if (lse && h == 0) lse[am_stat(Tfull, P, H, b, head, qrow)] = (m + __log2f(lt)) * 0.6931471805599453f;
     }
 }
@@ -356,7 +472,7 @@ __global__ __launch_bounds__(512) void attn_fwd_resident(const bf16_t *__restric
                 dot = fmaf(h16<F>::hi(kw[e]), h16<F>::hi(qw[e]), dot);
             }
         }
-        m[qt] = lane_xor32_sum(dot) * c;
+        m[qt] = xor32_sum(dot) * c;
         l[qt] = h == 0 ? 1.0f : 0.0f;
 #pragma unroll
         for (int dtile = 0; dtile < 2; ++dtile)
@@ -411,7 +527,7 @@ __global__ __launch_bounds__(512) void attn_fwd_resident(const bf16_t *__restric
             for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) mx = fmaxf(mx, st[qt][sub][e]);
-            mx = lane_xor32_max(mx);
+            mx = xor32_max(mx);
             const float mn = fmaxf(m[qt], mx * c);
             const float alpha = __builtin_amdgcn_exp2f(m[qt] - mn);
             m[qt] = mn;
@@ -466,7 +582,7 @@ __global__ __launch_bounds__(512) void attn_fwd_resident(const bf16_t *__restric
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
             const int qrow = q0 + 32 * qt + r;
-            const float lt = lane_xor32_sum(l[qt]);
+            const float lt = xor32_sum(l[qt]);
             const float inv = 1.0f / lt;
             bf16_t *ob = out + ((int64_t)b * T + qrow) * (H * HD) + head * HD;
 #pragma unroll
@@ -551,22 +667,6 @@ __global__ __launch_bounds__(512) void attn_fwd_resident(const bf16_t *__restric
 // Tiles that are read both row-wise (ds_read_b128) and transposed (ds_read_b64_tr_b16) are kept as
 // two LDS images, each with the swizzle that makes its read conflict-free.
 // =================================================================================================
-template <typename F>
-__device__ __forceinline__ uint4 pack8(const f32x16_t &x, int s)
-{
-    const uint4 u = make_uint4(h16<F>::pack2(x[8 * s + 0], x[8 * s + 1]), h16<F>::pack2(x[8 * s + 2], x[8 * s + 3]),
-                               h16<F>::pack2(x[8 * s + 4], x[8 * s + 5]), h16<F>::pack2(x[8 * s + 6], x[8 * s + 7]));
-    return (u);
-}
-
-__device__ __forceinline__ uint4 tr_frag(const unsigned char *img, int row0, int dbyte)
-{
-    struct { s4_t a, b; } f;
-    f.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4_t *)(img + v_off(row0, dbyte)));
-    f.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4_t *)(img + v_off(row0 + 8, dbyte)));
-    return __builtin_bit_cast(uint4, f);
-}
-
 // sum over the eight bf16 pairs of two 16-byte chunks (fp32)
 template <typename F>
 __device__ __forceinline__ float dot8_bf16(uint4 a, uint4 b)
@@ -580,9 +680,6 @@ __device__ __forceinline__ float dot8_bf16(uint4 a, uint4 b)
     }
     return acc;
 }
-
-constexpr int QT = 32;                       // query rows per staged tile in the dK/dV kernel
-constexpr int QTILE = QT * 128;              // bytes per 32-row image
 
 constexpr int DKV_SMEM = 2 * (4 * QTILE + 256);   // per stage: Q row image, Q tr image, dO row image, dO tr image (4 KiB each) + lse2[32] + delta[32]
 
@@ -813,7 +910,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const bf16_t *__restrict__ qkv,
     const float l2 = own ? lse[am_stat(Tfull, P, H, b, head, qrow)] * 1.4426950408889634f : INFINITY;
     float dl;
     if constexpr (INLINE_DELTA) {
-        const float ds = lane_xor32_sum(dsum);            // (both halves of the pair run it: same row, same `own`)
+        const float ds = xor32_sum(dsum);            // (both halves of the pair run it: same row, same `own`)
         dl = own ? ds : 0.f;
     } else dl = own ? delta[am_stat(Tfull, P, H, b, head, qrow)] : 0.f;
 
@@ -1163,6 +1260,30 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_tiny_mfma(const bf16_t *__res
 
 }  // namespace
 
+template <int FORM>
+static int launch_fwd_stream(const void *qkv, void *out, float *lse, int Bt, int T, int H, float scale, int causal, int P, hipStream_t s)
+{
+    using E = typename AttnForm<FORM>::T;
+    static const int xcd_map = getenv("PPT_ATTN_XCD_MAP") == nullptr || atoi(getenv("PPT_ATTN_XCD_MAP")) != 0;
+    const float c = scale * 1.4426950408889634f;
+    const int prio = ppt_get_wave_priority();
+    const dim3 grid((T + QB - 1) / QB, (Bt + (P > 0)) * H), block(256);
+    if (causal) hipLaunchKernelGGL((attn_fwd_stream<FORM, true>), grid, block, 0, s, (const E *)qkv, (E *)out, lse, T, H, c, P, Bt, prio, xcd_map);
+    else hipLaunchKernelGGL((attn_fwd_stream<FORM, false>), grid, block, 0, s, (const E *)qkv, (E *)out, lse, T, H, c, P, Bt, prio, xcd_map);
+    PPT_CHECK_LAUNCH();
+    return PPT_OK;
+}
+
+// The streaming forward in the form `form` (PPT_BF16, PPT_F16, or PPT_F32 = split16); the callers have checked the arguments and
+// the alignment (16-bit: qkv 16, out 8 bytes; split16: both 16).
+extern "C" int ppt_attention_fwd_stream(const void *qkv, void *out, float *lse, int Bt, int T, int H, float scale, int causal, int P,
+                                        int form, hipStream_t s)
+{
+    if (form == PPT_F32) return launch_fwd_stream<PPT_F32>(qkv, out, lse, Bt, T, H, scale, causal, P, s);
+    if (form == PPT_F16) return launch_fwd_stream<PPT_F16>(qkv, out, lse, Bt, T, H, scale, causal, P, s);
+    return launch_fwd_stream<PPT_BF16>(qkv, out, lse, Bt, T, H, scale, causal, P, s);
+}
+
 // fmt = PPT_BF16 or PPT_F16 (the 16-bit operand format of qkv / out / dout / dqkv) for the functions below
 extern "C" int ppt_attention_fwd_mfma_bf16(const void *qkv, void *out, float *lse, int Bt, int T, int H, float scale,
                                            int causal, int P, int fmt, hipStream_t s)
@@ -1189,18 +1310,7 @@ extern "C" int ppt_attention_fwd_mfma_bf16(const void *qkv, void *out, float *ls
         PPT_CHECK_LAUNCH();
         return PPT_OK;
     }
-    dim3 grid((T + QB - 1) / QB, (Bt + (P > 0)) * H);
-    const dim3 block(256);
-    static const int xcd_map = getenv("PPT_ATTN_XCD_MAP") == nullptr || atoi(getenv("PPT_ATTN_XCD_MAP")) != 0;
-    if (fmt == PPT_F16) {
-        if (causal) hipLaunchKernelGGL((attn_fwd_mfma<true, f16_t>), grid, block, 0, s, (const bf16_t *)qkv, (bf16_t *)out, lse, T, H, c, P, Bt, prio, xcd_map);
-        else hipLaunchKernelGGL((attn_fwd_mfma<false, f16_t>), grid, block, 0, s, (const bf16_t *)qkv, (bf16_t *)out, lse, T, H, c, P, Bt, prio, xcd_map);
-    } else {
-        if (causal) hipLaunchKernelGGL((attn_fwd_mfma<true, bf16_t>), grid, block, 0, s, (const bf16_t *)qkv, (bf16_t *)out, lse, T, H, c, P, Bt, prio, xcd_map);
-        else hipLaunchKernelGGL((attn_fwd_mfma<false, bf16_t>), grid, block, 0, s, (const bf16_t *)qkv, (bf16_t *)out, lse, T, H, c, P, Bt, prio, xcd_map);
-    }
-    PPT_CHECK_LAUNCH();
-    return PPT_OK;
+    return ppt_attention_fwd_stream(qkv, out, lse, Bt, T, H, scale, causal, P, fmt, s);
 }
 
 // dq / dk / dv of the bf16 path; `delta` must already hold rowsum(dO * O) (attention.hip: attn_delta).  P > 0 (prefix-shared

@@ -1,4 +1,4 @@
-// attn_rowmap.h -- row addressing shared by the attention kernels (attention.hip, attention_mfma.hip).
+// attn_rowmap.h -- row addressing shared by the attention kernels (attention.hip, attention_mfma.hip, attention_split.hip).
 //
 // Plain layout (P == 0): sequence v of Bt, position pos -> row v * T + pos of the packed [Bt * T, 3, H, 64] qkv tensor;
 // softmax statistics (LSE, delta) at [(v * H + head) * T + pos].

@@ -743,19 +743,35 @@ def layernorm_bwd(dy, xs, w, mean, rstd, dx=None, accumulate=False, want_wgrad=F
     return (dx, dw, db, cp) if copy_dtype is not None else (dx, dw, db)
 
 
-def attention_fwd(qkv, Bt, T, H, scale, causal, want_lse=True):
-    """qkv [Bt*T, 3*H*64] -> out [Bt*T, H*64], lse [Bt,H,T] f32."""
+def _attn_split16(qkv):
+    """split16 mode: fp32 q / k / v with every product from hi + lo half pairs on the matrix pipe"""
+    return qkv.dtype == torch.float32 and _SPLIT16 and ATTN_SPLIT16
+
+
+def _attn_pairs(n_seq, T, P, causal):
+    """(query, key) pairs per head of n_seq sequences of T positions whose first P (causal only) are stored and computed once"""
+    return n_seq * (T * T - P * P) + P * P if causal else 2 * n_seq * T * T
+
+
+def _attention_fwd(qkv, n_seq, T, P, H, scale, causal, want_lse):
+    """plain (P == 0: rows = n_seq * T, lse [n_seq, H, T]) or prefix-shared (P > 0, causal: lse [rows, H]) forward"""
     _chk(qkv, None, "qkv")
-    out = torch.empty((Bt * T, H * 64), dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty((Bt, H, T), dtype=torch.float32, device=qkv.device) if want_lse else None
+    rows = prefix_rows(n_seq, T, P)
+    assert not P or qkv.shape[0] == rows
+    out = torch.empty((rows, H * 64), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((rows, H) if P else (n_seq, H, T), dtype=torch.float32, device=qkv.device) if want_lse else None
     if profiler is not None:
-        profiler.begin("attention_fwd", 4.0 * Bt * H * T * T * 64 * (0.5 if causal else 1.0))
-    if qkv.dtype == torch.float32 and _SPLIT16 and ATTN_SPLIT16:      # split16 mode: both products from hi + lo half pairs
-        _lib.check(_lib.lib().ppt_attention_fwd_split16(_p(qkv), _p(out), _p(lse), Bt, T, 0, H, 64, scale, int(causal), _stream()),
+        profiler.begin("attention_fwd", 2.0 * _attn_pairs(n_seq, T, P, causal) * H * 64)
+    L = _lib.lib()
+    if _attn_split16(qkv):
+        _lib.check(L.ppt_attention_fwd_split16(_p(qkv), _p(out), _p(lse), n_seq, T, P, H, 64, scale, int(causal), _stream()),
                    "ppt_attention_fwd_split16")
+    elif P:
+        _lib.check(L.ppt_attention_prefix_fwd(_p(qkv), _p(out), _p(lse), n_seq, T, P, H, 64, scale, dtype_code(qkv), _stream()),
+                   "ppt_attention_prefix_fwd")
     else:
-        _lib.check(_lib.lib().ppt_attention_fwd(_p(qkv), _p(out), _p(lse), Bt, T, H, 64, scale, int(causal),
-                                                dtype_code(qkv), _stream()), "ppt_attention_fwd")
+        _lib.check(L.ppt_attention_fwd(_p(qkv), _p(out), _p(lse), n_seq, T, H, 64, scale, int(causal), dtype_code(qkv), _stream()),
+                   "ppt_attention_fwd")
     if profiler is not None:
         profiler.end()
     if probe is not None:
@@ -763,21 +779,35 @@ def attention_fwd(qkv, Bt, T, H, scale, causal, want_lse=True):
     return out, lse
 
 
-def attention_bwd(qkv, out, dout, lse, Bt, T, H, scale, causal):
+def _attention_bwd(qkv, out, dout, lse, n_seq, T, P, H, scale, causal):
     _chk(qkv, None, "qkv"); _chk(out, qkv.dtype, "out"); _chk(dout, qkv.dtype, "dout")
     dqkv = torch.empty_like(qkv)
-    delta = torch.empty((Bt, H, T), dtype=torch.float32, device=qkv.device)
+    delta = torch.empty((prefix_rows(n_seq, T, P), H) if P else (n_seq, H, T), dtype=torch.float32, device=qkv.device)
+    L = _lib.lib()
+    ws = torch.empty((L.ppt_attention_prefix_workspace_bytes(n_seq, P, H, 64) // 4,), dtype=torch.float32, device=qkv.device) if P else None
     if profiler is not None:
-        profiler.begin("attention_bwd", 10.0 * Bt * H * T * T * 64 * (0.5 if causal else 1.0))
-    if qkv.dtype == torch.float32 and _SPLIT16 and ATTN_SPLIT16:      # split16 mode: every product from hi + lo half pairs
-        _lib.check(_lib.lib().ppt_attention_bwd_split16(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), None, Bt, T, 0, H, 64,
-                                                        scale, int(causal), _stream()), "ppt_attention_bwd_split16")
+        profiler.begin("attention_bwd", 5.0 * _attn_pairs(n_seq, T, P, causal) * H * 64)
+    if _attn_split16(qkv):
+        _lib.check(L.ppt_attention_bwd_split16(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), _p(ws), n_seq, T, P, H, 64,
+                                               scale, int(causal), _stream()), "ppt_attention_bwd_split16")
+    elif P:
+        _lib.check(L.ppt_attention_prefix_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), _p(ws), n_seq, T, P, H, 64,
+                                              scale, dtype_code(qkv), _stream()), "ppt_attention_prefix_bwd")
     else:
-        _lib.check(_lib.lib().ppt_attention_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), Bt, T, H, 64,
-                                                scale, int(causal), dtype_code(qkv), _stream()), "ppt_attention_bwd")
+        _lib.check(L.ppt_attention_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), n_seq, T, H, 64,
+                                       scale, int(causal), dtype_code(qkv), _stream()), "ppt_attention_bwd")
     if profiler is not None:
         profiler.end()
     return dqkv
+
+
+def attention_fwd(qkv, Bt, T, H, scale, causal, want_lse=True):
+    """qkv [Bt*T, 3*H*64] -> out [Bt*T, H*64], lse [Bt,H,T] f32."""
+    return _attention_fwd(qkv, Bt, T, 0, H, scale, causal, want_lse)
+
+
+def attention_bwd(qkv, out, dout, lse, Bt, T, H, scale, causal):
+    return _attention_bwd(qkv, out, dout, lse, Bt, T, 0, H, scale, causal)
 
 
 def prefix_rows(C, T, P):
@@ -788,43 +818,11 @@ def prefix_rows(C, T, P):
 def attention_prefix_fwd(qkv, C, T, P, H, scale, want_lse=True):
     """causal attention over C prompts of T positions sharing their first P: qkv [P + C(T-P), 3*H*64] ->
     (out [rows, H*64], lse [rows, H] f32)."""
-    _chk(qkv, None, "qkv")
-    rows = prefix_rows(C, T, P)
-    assert qkv.shape[0] == rows
-    out = torch.empty((rows, H * 64), dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty((rows, H), dtype=torch.float32, device=qkv.device) if want_lse else None
-    if profiler is not None:
-        profiler.begin("attention_fwd", 2.0 * (C * (T * T - P * P) + P * P) * H * 64)
-    if qkv.dtype == torch.float32 and _SPLIT16 and ATTN_SPLIT16:
-        _lib.check(_lib.lib().ppt_attention_fwd_split16(_p(qkv), _p(out), _p(lse), C, T, P, H, 64, scale, 1, _stream()),
-                   "ppt_attention_fwd_split16")
-    else:
-        _lib.check(_lib.lib().ppt_attention_prefix_fwd(_p(qkv), _p(out), _p(lse), C, T, P, H, 64, scale, dtype_code(qkv), _stream()),
-                   "ppt_attention_prefix_fwd")
-    if profiler is not None:
-        profiler.end()
-    if probe is not None:
-        _probe("attention", out)
-    return out, lse
+    return _attention_fwd(qkv, C, T, P, H, scale, True, want_lse)
 
 
 def attention_prefix_bwd(qkv, out, dout, lse, C, T, P, H, scale):
-    _chk(qkv, None, "qkv"); _chk(out, qkv.dtype, "out"); _chk(dout, qkv.dtype, "dout")
-    rows = prefix_rows(C, T, P)
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty((rows, H), dtype=torch.float32, device=qkv.device)
-    ws = torch.empty((_lib.lib().ppt_attention_prefix_workspace_bytes(C, P, H, 64) // 4,), dtype=torch.float32, device=qkv.device)
-    if profiler is not None:
-        profiler.begin("attention_bwd", 5.0 * (C * (T * T - P * P) + P * P) * H * 64)
-    if qkv.dtype == torch.float32 and _SPLIT16 and ATTN_SPLIT16:
-        _lib.check(_lib.lib().ppt_attention_bwd_split16(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), _p(ws), C, T, P, H, 64,
-                                                        scale, 1, _stream()), "ppt_attention_bwd_split16")
-    else:
-        _lib.check(_lib.lib().ppt_attention_prefix_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), _p(ws), C, T, P, H, 64,
-                                                       scale, dtype_code(qkv), _stream()), "ppt_attention_prefix_bwd")
-    if profiler is not None:
-        profiler.end()
-    return dqkv
+    return _attention_bwd(qkv, out, dout, lse, C, T, P, H, scale, True)
 
 
 def conv1_stats(pts, w1, b1):

@@ -1865,8 +1865,8 @@ def test_gemm_split16_saturates_a_finite_overflow_and_counts_it(ops, M, N, K):
     ("prefix of one", 6, 20, 2, True, 1, 1.0),
 ])
 def test_attention_split16_forward_is_fp32_grade(ops, name, Bt, T, H, causal, P, gain):
-    """csrc/attention_split.hip (K.Q^T and V^T.P from hi + lo half pairs on the matrix pipe, fp32 softmax) against the fp32 VALU
-    kernel -- same layouts, prefix-shared included -- and against an fp64 softmax(QK^T)V."""
+    """The split16 form of csrc/attention_mfma.hip's streaming forward (K.Q^T and V^T.P from hi + lo half pairs on the matrix pipe, fp32
+    softmax) against the fp32 VALU kernel -- same layouts, prefix-shared included -- and against an fp64 softmax(QK^T)V."""
     g = torch.Generator().manual_seed(T + P)
     rows = Bt * T if P == 0 else ops.prefix_rows(Bt, T, P)
     qkv = (torch.randn(rows, 3 * H * 64, generator=g) * gain).cuda()

@@ -14,7 +14,9 @@ import pandas as pd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the bf16 MFMA GEMM family (what bench.py's roofline object is about): tile GEMMs, the fused mini-PointNet kernels, the
-# weight-stationary short-K linears and the fused ViT MLP (text_mlp_kernel<FORM, ..>: FORM 1 = PPT_BF16, 2 = PPT_F16; 0 is its split16 form)
+# weight-stationary short-K linears and the fused ViT MLP (text_mlp_kernel<FORM, ..>: FORM 1 = PPT_BF16, 2 = PPT_F16; 0 is its split16 form).
+# The attention kernels are not part of it, neither form of attn_fwd_stream<FORM, ..>: they join the MFMA-utilisation table by their
+# attn_ name, each instantiation a row of its own.
 GEMM_BF16 = r"gemm_kernel.*<(unsigned short|f16_t)|gemm256_kernel|gemm_tn_kernel|mpn[134]_kernel|rowgemm_kernel|vit_mlp_kernel|vit_mlp3_kernel|text_mlp_kernel<[12],|lnlin_kernel"
 CONFIGS = ("c2", "c3", "c4", "c5", "mlp")
 TRACE_STEPS = 40 + 5 + 10                   # burn-in + warm-up + timed steps of the traced command
