@@ -47,7 +47,8 @@ const char *ppt_strerror(int code);
  *    ppt_text_mlp_retile (new: csrc/text_mlp.hip), ppt_lnlin / ppt_lnlin_retile (new: csrc/lnlin.hip),
  *    ppt_text_mlp_retile_split + the split16 fields of ppt_text_mlp_params (csrc/text_mlp.hip), ppt_text_lin_split /
  *    ppt_text_lin_retile_split (csrc/text_lin.hip); later, additive only (no existing signature or struct changed):
- *    ppt_text_lin16 / ppt_text_lin_retile16 (the 16-bit form of ppt_text_lin_split); ppt_cloud_prep_f32 / ppt_cloud_draws (csrc/cloud_prep.hip).
+ *    ppt_text_lin16 / ppt_text_lin_retile16 (the 16-bit form of ppt_text_lin_split); ppt_cloud_prep_f32 / ppt_cloud_draws (csrc/cloud_prep.hip);
+ *    ppt_cls_metrics / ppt_partseg_metrics / ppt_partseg_metrics_chunks (csrc/metrics.hip).
  * 6: ppt_gemm_params.split16 / split_a_pow2 / split_b_pow2 (new trailing fields: fp32 operands as hi + lo half pairs),
  *    ppt_attention_fwd_split16 / ppt_attention_bwd_split16 (new), ppt_pointmlp_cloud_rstd / ppt_pointmlp_pq (new).
  * 5: ppt_labels_check (new), ppt_gemm256 (new: the 256-row macro-tile GEMM core), ppt_set_gemm256 / ppt_get_gemm256 (new),
@@ -760,6 +761,45 @@ int ppt_cloud_prep_f32(const float *src, int M, int Nmax, int C, const int32_t *
 int ppt_cloud_draws(const int64_t *index, int B, const int32_t *rows, int rows_all, int n, uint64_t seed, uint32_t epoch,
                     int64_t *start, double *scale, double *shift, int32_t *perm, int64_t *sel, const uint32_t *raw_ctr,
                     int raw_count, uint32_t *raw_out, void *stream);
+
+/* ---- validation metrics (ABI 7, additive; csrc/metrics.hip; host side: ppt_amd/evaluate.py) ---------------------------------
+ * What the reference's validate() loops take out of a batch of logits, as one launch per batch and one small record per sample;
+ * the host reads the records once per epoch.  fp32 logits, int64 labels; nothing is allocated, nothing synchronises; no
+ * floating-point atomics and a fixed summation order: two runs write identical bytes.
+ *
+ * cls_metrics replaces `criterion` + utils.accuracy (utils/utils.py:376-398) + the per-class counting of main_cls.py:266-284.
+ *   logits [B, C], labels [B]  ->  records [B, PPT_CLS_REC] int32 (16-byte aligned), per sample:
+ *     [0] the bits of the fp32 row loss (1 - s)(lse - x_t) + s (lse - mean_c x_c)   (nn.CrossEntropyLoss(label_smoothing = s), before
+ *         its mean over rows);
+ *     [1] the rank of the target: classes with a larger logit + classes with an equal logit at a lower index (top-1: rank 0,
+ *         top-k: rank < k);
+ *     [2] PPT_METRIC_NONFINITE: the row holds a non-finite logit (its rank is unspecified) | PPT_METRIC_BAD_LABEL: the label is
+ *         outside [0, C) (loss 0, rank C);
+ *     [3] the label (-1 when outside [0, C)). */
+#define PPT_METRIC_NONFINITE 1u
+#define PPT_METRIC_BAD_LABEL 2u
+#define PPT_CLS_REC 4
+int ppt_cls_metrics(const float *logits, const int64_t *labels, float smoothing, int B, int C, int32_t *records, void *stream);
+/* partseg_metrics replaces main_partseg.py:295-344: the masked arg-max, the accuracy count and the per-part IoU counts.
+ *   logits [B, N, P] (16-byte aligned), labels [B, N]; part_start / part_count [P] int32: for each part id its category's first
+ *   part and number of parts; max_parts: the largest entry of part_count (the tables are device memory).
+ *   P <= 64 and max_parts <= PPT_PARTSEG_MAX_PARTS, PPT_EUNSUPPORTED otherwise (nothing launched).
+ *   The cloud's category is the one labels[b, 0] belongs to (:302, :326 -- point 0's label, not the class label); a point's
+ *   prediction is the first arg-max over that category's part range, plus the range start (:305).
+ *   -> records [B, PPT_PARTSEG_REC] int32, per cloud:
+ *     [0] the category's first part   [1] its number of parts   [2] points with prediction == label
+ *     [3] PPT_METRIC_NONFINITE | PPT_METRIC_BAD_LABEL (any point; a bad labels[b, 0]: no category, all counts zero)
+ *     [4] the bits of the fp32 sum of the cloud's row losses over all P classes, unmasked, as `criterion` sees them (:295; rows
+ *         with a bad label add nothing)   [5] the number of chunks   [6], [7] zero
+ *     [8 + 3 j ..] for each part slot j < [1]: |gt = part|, |pred = part|, |gt = part and pred = part|; zero for j >= [1].
+ *   partial: scratch of B * ppt_partseg_metrics_chunks(N) floats.  A cloud is split over that many workgroups; they combine
+ *   their counts with integer atomics and their losses through one partial each, folded in chunk order by the last to arrive. */
+#define PPT_PARTSEG_REC 32
+#define PPT_PARTSEG_MAX_PARTS 8
+int ppt_partseg_metrics_chunks(int N);
+int ppt_partseg_metrics(const float *logits, const int64_t *labels, float smoothing, int B, int N, int P,
+                        const int32_t *part_start, const int32_t *part_count, int max_parts, int32_t *records, float *partial,
+                        void *stream);
 
 #ifdef __cplusplus
 }

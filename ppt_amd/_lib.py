@@ -241,6 +241,10 @@ _SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ppt_cloud_draws": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "ppt_cls_metrics": (c_int, [c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p]),
+    "ppt_partseg_metrics_chunks": (c_int, [c_int]),
+    "ppt_partseg_metrics": (c_int, [c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_void_p]),
 }
 
 

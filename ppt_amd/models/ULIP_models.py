@@ -1241,3 +1241,7 @@ def ULIP_PointBERT(args):
     params = sum(p.numel() for p in model.parameters() if p.requires_grad)
     print('\n====================\n\tNumber of learnable params:', params, '\n====================\n')
     return model
+
+
+# validate() of main_cls.py:237-299 / main_partseg.py:260-367 and utils.accuracy, on the device (ppt_amd/evaluate.py): part of the drop-in surface
+from ..evaluate import accuracy, validate, validate_partseg          # noqa: E402,F401

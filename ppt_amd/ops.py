@@ -1249,6 +1249,38 @@ def labels_check(labels, n_classes, ignore_index, flags, bit):
                "ppt_labels_check")
 
 
+METRIC_NONFINITE, METRIC_BAD_LABEL = 1, 2          # flag bits of the metric records (include/ppt_hip.h)
+CLS_REC, PARTSEG_REC, PARTSEG_MAX_PARTS = 4, 32, 8
+
+
+def cls_metrics(logits, labels, smoothing, records):
+    """logits [B, C] f32, labels [B] i64 -> records [B, 4] i32 (a caller-owned slice): per sample the bits of the row loss of
+    nn.CrossEntropyLoss(label_smoothing=smoothing), the rank of the target, the flag bits and the label (ppt_cls_metrics)."""
+    _chk(logits, torch.float32, "logits"); _chk(labels, torch.int64, "labels"); _chk(records, torch.int32, "records")
+    B, C = logits.shape
+    assert labels.shape == (B,) and records.shape == (B, CLS_REC)
+    _lib.check(_lib.lib().ppt_cls_metrics(_p(logits), _p(labels), float(smoothing), B, C, _p(records), _stream()), "ppt_cls_metrics")
+
+
+def partseg_metrics_chunks(N):
+    """workgroups one cloud of N points is split over (ppt_partseg_metrics_chunks): the scratch is B * chunks floats"""
+    return _lib.lib().ppt_partseg_metrics_chunks(int(N))
+
+
+def partseg_metrics(logits, labels, smoothing, part_start, part_count, max_parts, records, partial):
+    """logits [B, N, P] f32, labels [B, N] i64, part_start / part_count [P] i32 (per part id: its category's first part and
+    number of parts; max_parts = the largest count) -> records [B, 32] i32 (a caller-owned slice): per cloud the category's range,
+    the correct points, the loss sum and the per-part |gt|, |pred|, |gt and pred| (ppt_partseg_metrics; layout: include/ppt_hip.h).
+    partial: scratch of at least B * partseg_metrics_chunks(N) f32."""
+    _chk(logits, torch.float32, "logits"); _chk(labels, torch.int64, "labels"); _chk(records, torch.int32, "records")
+    _chk(part_start, torch.int32, "part_start"); _chk(part_count, torch.int32, "part_count"); _chk(partial, torch.float32, "partial")
+    B, N, P = logits.shape
+    assert labels.shape == (B, N) and records.shape == (B, PARTSEG_REC) and part_start.numel() == P and part_count.numel() == P
+    assert partial.numel() >= B * partseg_metrics_chunks(N)
+    _lib.check(_lib.lib().ppt_partseg_metrics(_p(logits), _p(labels), float(smoothing), B, N, P, _p(part_start), _p(part_count),
+                                              int(max_parts), _p(records), _p(partial), _stream()), "ppt_partseg_metrics")
+
+
 def health_check(x, flags, bit, maxabs=None):
     """flags[0] |= bit if x (any dtype, contiguous) holds a non-finite value; maxabs[0] = max(maxabs[0], max |finite x|) when
     given (ppt_health_check).  flags: int32 [1]; maxabs: f32 [1], non-negative."""
