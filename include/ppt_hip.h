@@ -182,7 +182,8 @@ typedef struct ppt_gemm_params {
 int ppt_gemm(const ppt_gemm_params *p, void *stream);
 /* The 256-row macro-tile core of ppt_gemm, called explicitly (csrc/gemm256.hip; ABI 5): 16-bit operands, a_mode PLAIN, K % 32 == 0,
  * K >= 64, no pooling; 256 x 256 output tiles per 512-thread workgroup (256 x 128 for narrow N), both operands through a ring of
- * LDS-DMA stages, the same epilogues.  ppt_gemm routes the large plain problems (every nn.Linear of the frozen ViT blocks over the
+ * LDS-DMA stages (four, two wave groups half a stage apart, at 256 columns; three, one barrier per stage, at 128), the same
+ * epilogues.  ppt_gemm routes the large plain problems (every nn.Linear of the frozen ViT blocks over the
  * 16 k-32 k token rows of a batch: point_encoder.py:14-30,46-58) here by itself; PPT_GEMM256=0 in the environment turns that off.
  * PPT_EUNSUPPORTED when the problem is outside these limits (nothing launched). */
 int ppt_gemm256(const ppt_gemm_params *p, void *stream);

@@ -47,13 +47,8 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(const ppt_gemm_params p)
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = w >> 1, wn = w & 1;
 #ifndef PPT_DBG_NO_XCD_SWIZZLE
-    // consecutive tiles (same m-tile, n fastest) onto one XCD: blocks are dealt round-robin over the 8
-    // XCDs, each with a private L2, so without this remap the column tiles that share one A row
-    // panel land on 8 different L2s (measured +5..8 % on the block GEMMs; speed only, never correctness)
     const int nwg = gridDim.x * gridDim.y;
-    const int lin0 = blockIdx.y * gridDim.x + blockIdx.x;
-    const int q8 = nwg / 8, r8 = nwg % 8, xcd = lin0 % 8;
-    const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + lin0 / 8;
+    const int lin = xcd_tile(blockIdx.y * gridDim.x + blockIdx.x, nwg);      // (gemm_common.h)
     const int n0 = (lin % gridDim.x) * BN, m0 = (lin / gridDim.x) * BM;
 #else
     const int n0 = blockIdx.x * BN, m0 = blockIdx.y * BM;
@@ -62,12 +57,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(const ppt_gemm_params p)
     const T *B = reinterpret_cast<const T *>(p.B) + (int64_t)blockIdx.z * p.strideB;
 
     f32x16_t acc[TI][TJ];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    PPT_ZERO_ACC(acc, TI, TJ);
     EpiPre<TI, TJ> epre;        // (the CONV1 prologue already fills the register file: it fetches these after the K loop)
     if constexpr (A_MODE != PPT_A_CONV1) epilogue_prefetch<TI, TJ>(p, epre, lane, m0 + wm * WM, n0 + wn * WN);
 
@@ -155,19 +145,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(const ppt_gemm_params p)
     }
 #endif
     float *ct = reinterpret_cast<float *>(smem) + w * (WM * WN);
-    {
-        const int h = lane >> 5, cl = lane & 31;
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-            for (int j = 0; j < TJ; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    ct[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * WN + j * 32 + cl] = acc[i][j][r];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    PPT_PARK_F32(acc, ct, lane, 0, TI, TJ);
 
     if (vec_epilogue_ok(p, zc)) epilogue_vec8<WM, WN>(p, ct, lane, m0 + wm * WM, n0 + wn * WN, zc);
     else epilogue_scalar<WM, WN>(p, ct, lane, m0 + wm * WM, n0 + wn * WN, m0, wm, zc);
@@ -208,19 +186,25 @@ __device__ __forceinline__ void glds_slab(const T *base, int64_t ld, int rows, i
 #else
 #define GEMM_STAMP(slot) do { } while (0)
 #endif
-// NSTAGE: LDS stages of the ring = slabs in flight + 1.  Three (48 KiB: three workgroups of the 64 x 64 tile per CU).  FOUR
-// (64 KiB, three slabs in flight) was measured for the prompt chain's small grids (<= 256 workgroups: one per CU whatever the
-// LDS size) after the LDS-DMA ring actually ran as a ring (ppt_common.h lds_dma16): 6.7 -> 6.9 us at K = 512, 13.0 -> 13.4 us at
-// K = 2048, C2 3.05 -> 3.10 ms -- the K loop is not short of bytes in flight, it runs at what ONE CU's LDS-DMA path takes
-// (~27 B/clk).  PPT_GEMM_DEEP_BELOW=<workgroups> selects it (default 0: never).  (Also measured and removed: four HELPER waves per
+// Three LDS stages = two slabs in flight (48 KiB: three workgroups of the 64 x 64 tile per CU).  Only the 64 x 64 tile is ever
+// launched.  The 128 x 128 instantiation stays compiled although launch_gemm_tile cannot reach it: it shares epilogue_vec8<64, 64>
+// and epilogue_scalar<64, 64> with gemm_kernel<T, A_MODE, 128, 128>, and with it gone the compiler schedules the epilogue of those
+// twelve live kernels differently (tools/kernel_isa_diff.py; profiles/r11_gemm_cleanup.md).  Removing it is a change of its own,
+// to be made with a timing of those kernels.
+// (Tried and removed: FOUR stages -- 64 KiB, three slabs in flight -- for the prompt chain's small grids (<= 256 workgroups: one per
+// CU whatever the LDS size) after the LDS-DMA ring actually ran as a ring (ppt_common.h lds_dma16): 6.7 -> 6.9 us at K = 512,
+// 13.0 -> 13.4 us at K = 2048, C2 3.05 -> 3.10 ms -- the K loop is not short of bytes in flight, it runs at what ONE CU's LDS-DMA
+// path takes (~27 B/clk).  Tried and removed: the 128 x 128 tile on this loop -- three 32 KiB stages leave one workgroup per CU:
+// measured slower than register staging.  Also measured and removed: four HELPER waves per
 // workgroup that only issue half of the DMA pieces and meet the barriers -- 12.6 -> 12.0 us at K = 2048 alone, C2 3.11 -> 3.19 ms in
 // the step: the rate is a property of the CU, not of how many waves ask, and 512-thread workgroups are harder to place beside the
 // tower.  And 32 x 64 tiles -- 208 two-wave workgroups, five 12 KiB stages, bit-identical results -- to put these 104-workgroup
 // launches on more CUs: 12.2 -> 12.8 us plain, 12.6 -> 17.1 us with the residual epilogue, C2 3.08 -> 3.35 ms.  Two waves do not
 // keep a CU's DMA path as busy as four.  The 64 x 64 / four-wave / three-stage kernel is where these shapes stay.)
-template <typename T, int BM, int BN, int NSTAGE = 3>
+template <typename T, int BM, int BN>
 __global__ __launch_bounds__(NT, BM == 64 ? 3 : 1) void gemm_kernel_glds(const ppt_gemm_params p)   // (a waves-per-SIMD floor keeps the accumulators out of AGPRs)
 {
+    constexpr int NSTAGE = 3;
     constexpr int WM = BM / 2, WN = BN / 2, TI = WM / 32, TJ = WN / 32;
     constexpr int A_BYTES = BM * ROWB, B_BYTES = BN * ROWB, STAGE = A_BYTES + B_BYTES;
     constexpr int LOADS_PER_SLAB = BM / 32 + BN / 32;    // LDS-DMA instructions per wave per slab
@@ -233,20 +217,13 @@ __global__ __launch_bounds__(NT, BM == 64 ? 3 : 1) void gemm_kernel_glds(const p
     PPT_PRIO(p.wave_prio);
     const int wm = w >> 1, wn = w & 1;
     const int nwg = gridDim.x * gridDim.y;
-    const int lin0 = blockIdx.y * gridDim.x + blockIdx.x;
-    const int q8 = nwg / 8, r8 = nwg % 8, xcd = lin0 % 8;
-    const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + lin0 / 8;
+    const int lin = xcd_tile(blockIdx.y * gridDim.x + blockIdx.x, nwg);
     const int n0 = (lin % gridDim.x) * BN, m0 = (lin / gridDim.x) * BM;
     const T *A = reinterpret_cast<const T *>(p.A) + (int64_t)blockIdx.z * p.strideA;
     const T *B = reinterpret_cast<const T *>(p.B) + (int64_t)blockIdx.z * p.strideB;
 
     f32x16_t acc[TI][TJ];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    PPT_ZERO_ACC(acc, TI, TJ);
     const int nslab = p.K / BK, last = nslab - 1;
     auto issue = [&](int slab, int stage) {
         glds_slab<T, BM>(A, p.lda, p.M, m0, slab * BK, smem + stage * STAGE, w, lane);
@@ -282,19 +259,7 @@ __global__ __launch_bounds__(NT, BM == 64 ? 3 : 1) void gemm_kernel_glds(const p
     }
 #endif
     float *ct = reinterpret_cast<float *>(smem) + w * (WM * WN);
-    {
-        const int h = lane >> 5, cl = lane & 31;
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-            for (int j = 0; j < TJ; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    ct[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * WN + j * 32 + cl] = acc[i][j][r];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    PPT_PARK_F32(acc, ct, lane, 0, TI, TJ);
     if (vec_epilogue_ok(p, zc)) epilogue_vec8<WM, WN>(p, ct, lane, m0 + wm * WM, n0 + wn * WN, zc);
     else epilogue_scalar<WM, WN>(p, ct, lane, m0 + wm * WM, n0 + wn * WN, m0, wm, zc);
 #ifdef PPT_GEMM_STAMP
@@ -313,126 +278,54 @@ __global__ __launch_bounds__(NT, BM == 64 ? 3 : 1) void gemm_kernel_glds(const p
 // slab = 28 B/clk per CU, the L2 -> LDS rate of one CU.)
 // =================================================================================================
 // Half-slab LDS-DMA kernel for the big plain-operand problems (qkv, fc1, conv3): 128x128 tiles, 64-byte K slabs
-// (32 bf16), 16 KiB stages: two of them (default; FOUR workgroups = 16 waves share a CU) or three (three workgroups).
+// (32 bf16), TWO 16 KiB stages (four workgroups = 16 waves share a CU, prefetch distance 1).
+// (Tried and removed: three stages -- 48 KiB, three workgroups, distance 2: 4.82 against 4.73 ms on C2, conv3 346 against 325 us.
+// The fill rate follows the wave count, tools/lds_fill_bench.hip, and a fourth co-resident workgroup hides more of the others'
+// epilogues.)
 // Why: tools/lds_fill_bench.hip shows that what a CU can pull out of L2 depends on how many waves are issuing --
 // 4 waves 6.5, 8 waves 11, 12 waves 14, 16 waves 16 TB/s over the chip -- and hardly on the bytes each keeps in
 // flight, and both existing tile loops sit on that line: 64x64 tiles (12 waves, 32 flop per LDS-fill byte) at
 // 11.4 of 14 TB/s, register-staged 128x128 (8 waves, 64 flop/B) at 10 of 11 TB/s.  This kernel takes the 64 flop/B
-// of the big tile AND the 12 waves.  It has only the register-layout epilogue (the fp32 park of epilogue_vec8 would
+// of the big tile AND 16 waves.  It has only the register-layout epilogue (the fp32 park of epilogue_vec8 would
 // need 64 KiB): the host sends it launches for which reg_epilogue_ok holds.
-// LDS image: 64-byte rows, 16-byte chunk c of row r at slot c ^ ((r >> 2) & 3): four consecutive rows fill one
-// 256-byte bank row, and the lane groups of ds_read_b128 ({0-3,12-15,20-27}, ...) then touch 16 distinct slots.
+// LDS image: gemm_common.h's 64-byte-row one (lds_off_h), filled by glds_half and read by mma_half.
 // =================================================================================================
-constexpr int ROWH = 64;
-__device__ __forceinline__ int lds_off_h(int row, int chunk) { return row * ROWH + ((chunk ^ ((row >> 2) & 3)) << 4); }
-
-template <typename T, int ROWS>
-__device__ __forceinline__ void glds_half(const T *base, int64_t ld, int rows, int r0, int k0, unsigned char *tile, int w, int lane)
-{
-    constexpr int EPC = 16 / sizeof(T);
-    constexpr int PER_WAVE = ROWS / 64;                  // 1 KiB pieces (16 rows) per wave
-#pragma unroll
-    for (int i = 0; i < PER_WAVE; ++i) {
-        const int rg = (w * PER_WAVE + i) * 16;
-        const int r = rg + (lane >> 2);
-        const int c = (lane & 3) ^ ((r >> 2) & 3);       // source chunk that belongs in LDS slot lane&3 of row r
-        const T *src = base + (int64_t)min(r0 + r, rows - 1) * ld + k0 + c * EPC;
-        lds_dma16(src, tile + rg * ROWH);
-    }
-}
-
-template <typename T, int TI, int TJ>
-__device__ __forceinline__ void mma_half(const unsigned char *As, const unsigned char *Bs, int arow0, int brow0, int lane,
-                                         f32x16_t (&acc)[TI][TJ])
-{
-    const int r = lane & 31, h = lane >> 5;
-    if constexpr (sizeof(T) == 2) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            uint4 a[TI], b[TJ];
-#pragma unroll
-            for (int i = 0; i < TI; ++i)
-                a[i] = *reinterpret_cast<const uint4 *>(As + lds_off_h(arow0 + i * 32 + r, kk * 2 + h));
-#pragma unroll
-            for (int j = 0; j < TJ; ++j)
-                b[j] = *reinterpret_cast<const uint4 *>(Bs + lds_off_h(brow0 + j * 32 + r, kk * 2 + h));
-#pragma unroll
-            for (int i = 0; i < TI; ++i)
-#pragma unroll
-                for (int j = 0; j < TJ; ++j)
-                    acc[i][j] = h16<T>::mfma32(a[i], b[j], acc[i][j]);
-        }
-    } else {
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-            const int kq = 2 * kk + h;      // k index (in floats) inside the 16-float slab
-            float a[TI], b[TJ];
-#pragma unroll
-            for (int i = 0; i < TI; ++i)
-                a[i] = *reinterpret_cast<const float *>(As + lds_off_h(arow0 + i * 32 + r, kq >> 2) + (kq & 3) * 4);
-#pragma unroll
-            for (int j = 0; j < TJ; ++j)
-                b[j] = *reinterpret_cast<const float *>(Bs + lds_off_h(brow0 + j * 32 + r, kq >> 2) + (kq & 3) * 4);
-#pragma unroll
-            for (int i = 0; i < TI; ++i)
-#pragma unroll
-                for (int j = 0; j < TJ; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-    }
-}
-
-template <typename T, int BM, int BN, int NSTAGE = 3, int EPI = -1>
-__global__ __launch_bounds__(NT, NSTAGE == 3 ? 3 : 4) void gemm_kernel_glds_h(const ppt_gemm_params p)
+template <typename T, int BM, int BN, int EPI = -1>
+__global__ __launch_bounds__(NT, 4) void gemm_kernel_glds_h(const ppt_gemm_params p)
 {
     constexpr int WM = BM / 2, WN = BN / 2, TI = WM / 32, TJ = WN / 32;
     constexpr int A_BYTES = BM * ROWH, B_BYTES = BN * ROWH, STAGE = A_BYTES + B_BYTES;
     constexpr int LOADS_PER_SLAB = BM / 64 + BN / 64;    // LDS-DMA instructions per wave per slab
-    static_assert(LOADS_PER_SLAB == 4, "counted vmcnt below");
+    static_assert(LOADS_PER_SLAB == 4, "one 1 KiB DMA piece per wave per 64 operand rows");
     constexpr int PARK_BYTES = 4 * WM * WN * 2;          // bf16 park of epilogue_regs
-    __shared__ __align__(16) unsigned char smem[NSTAGE * STAGE > PARK_BYTES ? NSTAGE * STAGE : PARK_BYTES];
+    __shared__ __align__(16) unsigned char smem[2 * STAGE > PARK_BYTES ? 2 * STAGE : PARK_BYTES];
     constexpr int BK = ROWH / sizeof(T);
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = w >> 1, wn = w & 1;
     const int nwg = gridDim.x * gridDim.y;
-    const int lin0 = blockIdx.y * gridDim.x + blockIdx.x;
-    const int q8 = nwg / 8, r8 = nwg % 8, xcd = lin0 % 8;                   // same XCD-aware remap as gemm_kernel
-    const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + lin0 / 8;
+    const int lin = xcd_tile(blockIdx.y * gridDim.x + blockIdx.x, nwg);
     const int n0 = (lin % gridDim.x) * BN, m0 = (lin / gridDim.x) * BM;
     const T *A = reinterpret_cast<const T *>(p.A) + (int64_t)blockIdx.z * p.strideA;
     const T *B = reinterpret_cast<const T *>(p.B) + (int64_t)blockIdx.z * p.strideB;
 
     f32x16_t acc[TI][TJ];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    PPT_ZERO_ACC(acc, TI, TJ);
     const int nslab = p.K / BK, last = nslab - 1;
     auto issue = [&](int slab, int stage) {
-        glds_half<T, BM>(A, p.lda, p.M, m0, slab * BK, smem + stage * STAGE, w, lane);
-        glds_half<T, BN>(B, p.ldb, p.N, n0, slab * BK, smem + stage * STAGE + A_BYTES, w, lane);
+        glds_half<T, BM, 4>(A, p.lda, p.M, m0, slab * BK, smem + stage * STAGE, w, lane);
+        glds_half<T, BN, 4>(B, p.ldb, p.N, n0, slab * BK, smem + stage * STAGE + A_BYTES, w, lane);
     };
     issue(0, 0);
-    if constexpr (NSTAGE == 3) issue(min(1, last), 1);
     EpiPre<TI, TJ> epre;                                  // (behind the first slabs: the K loop must not start later for it)
     epilogue_prefetch<TI, TJ>(p, epre, lane, m0 + wm * WM, n0 + wn * WN);
     int stage = 0;
     for (int s = 0; s < nslab; ++s) {
-        if constexpr (NSTAGE == 3) {
-            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // own copies of slab s landed (slab s+1's four may still fly)
-            __builtin_amdgcn_s_barrier();                     // ... and everybody else's: slab s is readable
-            int nstage = stage + 2; if (nstage >= NSTAGE) nstage -= NSTAGE;
-            issue(min(s + 2, last), nstage);                  // stage (s+2)%3 was last read at slab s-1, before this barrier
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            issue(min(s + 1, last), stage ^ 1);               // the other stage was last read at slab s-1, before this barrier
-        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // own copies of slab s have landed ...
+        __builtin_amdgcn_s_barrier();                         // ... and everybody else's: slab s is readable
+        issue(min(s + 1, last), stage ^ 1);                   // the other stage was last read at slab s-1, before this barrier
         mma_half<T, TI, TJ>(smem + stage * STAGE, smem + stage * STAGE + A_BYTES, wm * WM, wn * WN, lane, acc);
-        stage = stage + 1 == NSTAGE ? 0 : stage + 1;
+        stage = stage + 1 == 2 ? 0 : stage + 1;               // (not `stage ^= 1`: that form compiles to other K-loop code than the parent's)
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // surplus prefetches must not land on the parked tile
     __builtin_amdgcn_s_barrier();
@@ -441,11 +334,11 @@ __global__ __launch_bounds__(NT, NSTAGE == 3 ? 3 : 4) void gemm_kernel_glds_h(co
 }
 
 // host side of the choice: plain operands, K in whole half-slabs, an epilogue the register path covers for every
-// batch slice, and enough 128x128 tiles to give each CU its three workgroups
+// batch slice, and enough 128x128 tiles to give each CU its four workgroups
 template <typename T>
 bool glds_h_ok(const ppt_gemm_params &p, int64_t tiles128)
 {
-    static const int min_tiles = [] { const char *e = getenv("PPT_GEMM_H128_MIN"); return e ? atoi(e) : 768; }();
+    static const int min_tiles = env_int("PPT_GEMM_H128_MIN", 768);
     constexpr int BKH = ROWH / sizeof(T);
     if (p.a_mode != PPT_A_PLAIN || (p.K % BKH) != 0 || tiles128 < min_tiles) return false;
     if (p.batch > 1 && (p.strideC % 8) != 0) return false;
@@ -457,21 +350,16 @@ int launch_gemm_tile(const ppt_gemm_params &p, hipStream_t s)
 {
     dim3 grid((p.N + BN - 1) / BN, (p.M + BM - 1) / BM, p.batch > 0 ? p.batch : 1);
     if (grid.y > 65535 || grid.z > 65535) return PPT_EUNSUPPORTED;
-    static const int use_glds = [] { const char *e = getenv("PPT_GEMM_GLDS"); return e ? atoi(e) : 1; }();
+    static const int use_glds = env_int("PPT_GEMM_GLDS", 1);
     constexpr int BKE = ROWB / sizeof(T);
-    // (three 32 KiB stages of the 128x128 tile leave one workgroup per CU: measured slower than register staging)
-    if (!SPLIT && use_glds && BM == 64 && p.a_mode == PPT_A_PLAIN && p.K % BKE == 0) {   // (split16 splits between registers and LDS)
-        static const int deep_below = [] { const char *e = getenv("PPT_GEMM_DEEP_BELOW"); return e ? atoi(e) : 0; }();
-        if constexpr (BM == 64 && BN == 64) {
-            if ((int)(grid.x * grid.y * grid.z) < deep_below && p.K / BKE >= 4) {
-                hipLaunchKernelGGL((gemm_kernel_glds<T, 64, 64, 4>), grid, dim3(NT), 0, s, p);
-                PPT_CHECK_LAUNCH();
-                return PPT_OK;
-            }
+    // the LDS-DMA loop takes the plain-operand 64 x 64 launches (split16 splits between registers and LDS).  BM == 64 is tested at
+    // run time on purpose: that keeps gemm_kernel_glds<T, 128, 128> compiled (see the note above that kernel).
+    if constexpr (!SPLIT) {
+        if (use_glds && BM == 64 && p.a_mode == PPT_A_PLAIN && p.K % BKE == 0) {
+            hipLaunchKernelGGL((gemm_kernel_glds<T, BM, BN>), grid, dim3(NT), 0, s, p);
+            PPT_CHECK_LAUNCH();
+            return PPT_OK;
         }
-        hipLaunchKernelGGL((gemm_kernel_glds<T, BM, BN>), grid, dim3(NT), 0, s, p);
-        PPT_CHECK_LAUNCH();
-        return PPT_OK;
     }
     switch (p.a_mode) {
     case PPT_A_PLAIN: hipLaunchKernelGGL((gemm_kernel<T, PPT_A_PLAIN, BM, BN, SPLIT>), grid, dim3(NT), 0, s, p); break;
@@ -492,13 +380,13 @@ int launch_gemm_tile(const ppt_gemm_params &p, hipStream_t s)
 template <typename T, bool SPLIT = false>
 int launch_gemm(const ppt_gemm_params &p, hipStream_t s)
 {
-    static const int small_below = [] { const char *e = getenv("PPT_GEMM_SMALL_BELOW"); return e ? atoi(e) : 4096; }();
+    static const int small_below = env_int("PPT_GEMM_SMALL_BELOW", 4096);
     const int64_t tiles128 = (int64_t)((p.N + 127) / 128) * ((p.M + 127) / 128) * (p.batch > 0 ? p.batch : 1);
     const bool need128 = p.col_sum || p.pool_max;       // 32-row chunk partials / pools need 64-wide wave tiles
     if constexpr (SPLIT) {
         // split16: the register-staged kernel only (the split sits between its registers and LDS); 128 x 128 tiles (24 MFMAs per
         // 32 values a thread splits) as soon as they fill the chip, 64 x 64 (6 per 16) below
-        static const int split_small_below = [] { const char *e = getenv("PPT_SPLIT16_SMALL_BELOW"); return e ? atoi(e) : 512; }();
+        static const int split_small_below = env_int("PPT_SPLIT16_SMALL_BELOW", 512);
         // (measured and not kept: 128 x 64 tiles for narrow N over many rows -- fc2 of a C2 batch 115.7 vs 116.6 us)
         if (!need128 && tiles128 < split_small_below) return launch_gemm_tile<T, 64, 64, true>(p, s);
         return launch_gemm_tile<T, 128, 128, true>(p, s);
@@ -506,20 +394,11 @@ int launch_gemm(const ppt_gemm_params &p, hipStream_t s)
     if (glds_h_ok<T>(p, tiles128)) {
         dim3 grid((p.N + 127) / 128, (p.M + 127) / 128, p.batch > 0 ? p.batch : 1);
         if (grid.y > 65535 || grid.z > 65535) return PPT_EUNSUPPORTED;
-        // two stages (32 KiB, 4 workgroups = 16 waves per CU, prefetch distance 1) beat three (48 KiB, 3 workgroups,
-        // distance 2) in the step: 4.73 vs 4.82 ms on C2, conv3 346 -> 325 us -- the fill rate follows the wave count
-        // (tools/lds_fill_bench.hip) and a fourth co-resident workgroup hides more of the others' epilogues
-        static const int two_stage = [] { const char *e = getenv("PPT_GEMM_H128_STAGES"); return !(e && atoi(e) == 3); }();
-        if (two_stage) {
-            switch (p.C ? epi_mask(p) : -1) {           // the three hot epilogues have their own small kernels
-            case 0: hipLaunchKernelGGL((gemm_kernel_glds_h<T, 128, 128, 2, 0>), grid, dim3(NT), 0, s, p); break;
-            case EPI_GELU: hipLaunchKernelGGL((gemm_kernel_glds_h<T, 128, 128, 2, EPI_GELU>), grid, dim3(NT), 0, s, p); break;
-            case EPI_GROUP | EPI_STATS:
-                hipLaunchKernelGGL((gemm_kernel_glds_h<T, 128, 128, 2, EPI_GROUP | EPI_STATS>), grid, dim3(NT), 0, s, p); break;
-            default: hipLaunchKernelGGL((gemm_kernel_glds_h<T, 128, 128, 2>), grid, dim3(NT), 0, s, p); break;
-            }
-        } else {
-            hipLaunchKernelGGL((gemm_kernel_glds_h<T, 128, 128>), grid, dim3(NT), 0, s, p);
+        switch (p.C ? epi_mask(p) : -1) {               // the three hot epilogues have their own small kernels
+        case 0: hipLaunchKernelGGL((gemm_kernel_glds_h<T, 128, 128, 0>), grid, dim3(NT), 0, s, p); break;
+        case EPI_GELU: hipLaunchKernelGGL((gemm_kernel_glds_h<T, 128, 128, EPI_GELU>), grid, dim3(NT), 0, s, p); break;
+        case EPI_GROUP | EPI_STATS: hipLaunchKernelGGL((gemm_kernel_glds_h<T, 128, 128, EPI_GROUP | EPI_STATS>), grid, dim3(NT), 0, s, p); break;
+        default: hipLaunchKernelGGL((gemm_kernel_glds_h<T, 128, 128>), grid, dim3(NT), 0, s, p); break;
         }
         PPT_CHECK_LAUNCH();
         return PPT_OK;
@@ -539,7 +418,7 @@ extern "C" int ppt_gemm(const ppt_gemm_params *pp, void *stream)
     ppt_gemm_params q = *pp;
     if (!q.wave_prio) q.wave_prio = ppt_get_wave_priority();
     const ppt_gemm_params &p = q;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || !p.B) return PPT_EINVAL;
+    if (const int rc = validate_dims(p)) return rc;     // (validate_*: the checks ppt_gemm256 shares, gemm_common.h)
     if (p.dtype != PPT_F32 && p.dtype != PPT_BF16 && p.dtype != PPT_F16) return PPT_EINVAL;
     if (p.split16 && (p.dtype != PPT_F32 || abs(p.split_a_pow2) > 24 || abs(p.split_b_pow2) > 24)) return PPT_EINVAL;
     // one 16-bit format per GEMM: outputs / saved pre-activations / pooled rows are fp32 or the operands' format
@@ -564,10 +443,7 @@ extern "C" int ppt_gemm(const ppt_gemm_params *pp, void *stream)
 #endif
     if ((p.col_sum || p.pool_max) && ((p.N % 8) || ((uintptr_t)p.pool_min & 15) || ((uintptr_t)p.col_sum & 15) || ((uintptr_t)p.col_sqsum & 15) || ((uintptr_t)p.pool_max & 15)))
         return PPT_EUNSUPPORTED;                       // statistics / pooling exist only in the 16-byte epilogue
-    if (p.group_add && p.group_rows <= 0) return PPT_EINVAL;
-    if (p.row_scale && p.row_scale_rows <= 0) return PPT_EINVAL;
-    if (p.batch > 1 && (p.C2 || p.col_sum || p.pool_max || p.residual || p.residual2 || p.dact_pre || p.group_add))
-        return PPT_EUNSUPPORTED;
+    if (const int rc = validate_operands(p)) return rc;
     if (ppt_gemm256_dispatch(&p, 0, stream) == PPT_OK) return PPT_OK;     // the 256-row macro-tile core takes the big plain problems
     hipStream_t s = ppt_stream(stream);
     if (p.dtype == PPT_F32 && p.split16) {                                        // hi + lo half products (gemm_common.h, split16)

@@ -8,20 +8,17 @@
 // Geometry.  512 threads = 8 waves, ONE workgroup per CU for the 256 x 256 tile (waves 2 x 4, each 128 x 64 = 4 x 2 MFMA tiles of
 // 32 x 32: 128 accumulator registers), two for the 256 x 128 tile (waves 4 x 2, each 64 x 64: 64 accumulators, 128 VGPRs per wave).
 // K is walked in 64-BYTE half-slabs (32 values) through a ring of LDS stages filled by LDS-DMA (global_load_lds_dwordx4, the
-// XOR swizzle applied to the source address: ppt_common.h lds_dma16, gemm.hip gemm_kernel_glds_h), counted vmcnt, one raw s_barrier
-// per stage, NSTAGE - 1 stages in flight.  The epilogues are gemm_common.h's: the register-layout one (bias / GELU / per-group term +
-// BatchNorm partials; compile-time variants) and, for row-major fp32 operands (the residual stream of proj / fc2), the 16-byte LDS
-// walk over an fp32 park, taken in two 64-row halves for the 128-row wave tile.
+// XOR swizzle applied to the source address: ppt_common.h lds_dma16, gemm_common.h glds_half / mma_half -- the helpers of gemm.hip's
+// gemm_kernel_glds_h), counted vmcnt, NSTAGE - 1 stages in flight.  The schedule follows the tile width: the 256 x 256 tile (four
+// stages, one workgroup per CU) runs the STAGGERED loop -- two wave groups half a stage apart --, the 256 x 128 tile (three stages,
+// two workgroups per CU) one raw s_barrier per stage.  The epilogues are gemm_common.h's: the register-layout one (bias / GELU /
+// per-group term + BatchNorm partials; compile-time variants) and, for row-major fp32 operands (the residual stream of proj /
+// fc2), the 16-byte LDS walk over an fp32 park, 32 rows of the wave tile at a time.
 #include "gemm_common.h"
 
 namespace {
 
-constexpr int NT2 = 512, ROWH = 64;
-#ifdef PPT_GEMM256_WHOLE_EPILOGUE
-constexpr bool SLICED_EPILOGUE = false;        // (A/B builds: the whole-tile register epilogue of gemm_common.h)
-#else
-constexpr bool SLICED_EPILOGUE = true;
-#endif
+constexpr int NT2 = 512;
 
 // Diagnostic build only (tools/gemm256_stamp.py compiles this file with -DPPT_GEMM_STAMP into its own library): lane 0 of every wave
 // stores s_memtime at entry / prologue DMA issued / first stage readable / K loop done / stores done into the buffer p.pool_min
@@ -31,45 +28,6 @@ constexpr bool SLICED_EPILOGUE = true;
 #else
 #define G256_STAMP(slot) do { } while (0)
 #endif
-__device__ __forceinline__ int lds_off_h(int row, int chunk) { return row * ROWH + ((chunk ^ ((row >> 2) & 3)) << 4); }
-
-// ROWS x 64 bytes of an operand -> LDS, by the NW waves of the workgroup: ROWS / (16 NW) pieces of 1 KiB (16 rows) per wave
-template <typename T, int ROWS, int NW = 8>
-__device__ __forceinline__ void glds_half8(const T *base, int64_t ld, int rows, int r0, int k0, unsigned char *tile, int w, int lane)
-{
-    constexpr int EPC = 16 / sizeof(T);
-    constexpr int PER_WAVE = ROWS / (16 * NW);
-#pragma unroll
-    for (int i = 0; i < PER_WAVE; ++i) {
-        const int rg = (w * PER_WAVE + i) * 16;
-        const int r = rg + (lane >> 2);
-        const int c = (lane & 3) ^ ((r >> 2) & 3);       // source chunk that belongs in LDS slot lane&3 of row r
-        const T *src = base + (int64_t)min(r0 + r, rows - 1) * ld + k0 + c * EPC;
-        lds_dma16(src, tile + rg * ROWH);
-    }
-}
-
-template <typename T, int TI, int TJ>
-__device__ __forceinline__ void mma_half8(const unsigned char *As, const unsigned char *Bs, int arow0, int brow0, int lane,
-                                          f32x16_t (&acc)[TI][TJ])
-{
-    const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-        uint4 a[TI], b[TJ];
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-            b[j] = *reinterpret_cast<const uint4 *>(Bs + lds_off_h(brow0 + j * 32 + r, kk * 2 + h));
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-            a[i] = *reinterpret_cast<const uint4 *>(As + lds_off_h(arow0 + i * 32 + r, kk * 2 + h));
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-            for (int j = 0; j < TJ; ++j)
-                acc[i][j] = h16<T>::mfma32(a[i], b[j], acc[i][j]);
-    }
-}
 
 // The two halves of a stage's work as separate steps (the staggered schedule below): all fragments of a 32-deep stage into
 // registers (6 x 2 ds_read_b128 for the 128 x 64 wave tile), then 16 MFMAs on registers only.
@@ -198,24 +156,14 @@ template <int HALF, int PR, int TI, int TJ>
 __device__ __forceinline__ void park_walk(const ppt_gemm_params &p, f32x16_t (&acc)[TI][TJ], float *ct, int lane, int mw, int nw, int64_t zc)
 {
     constexpr int WN = TJ * 32;
-    const int h = lane >> 5, cl = lane & 31;
-#pragma unroll
-    for (int i = 0; i < PR / 32; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                ct[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * WN + j * 32 + cl] = acc[HALF * (PR / 32) + i][j][r];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    PPT_PARK_F32(acc, ct, lane, HALF * (PR / 32), PR / 32, TJ);
     epilogue_vec8<PR, WN, 1>(p, ct, lane, mw + HALF * PR, nw, zc);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <typename T, int BN, int NSTAGE, int EPI, bool PP>
+template <typename T, int BN, int NSTAGE, int EPI>
 // (the LDS-walk epilogue of the EPI < 0 kernels needs more than the 128 registers that two workgroups per CU would leave)
 __global__ __launch_bounds__(NT2, (BN == 256 || EPI < 0) ? 2 : 4) void gemm256_kernel(const ppt_gemm_params p)
 {
@@ -237,38 +185,18 @@ __global__ __launch_bounds__(NT2, (BN == 256 || EPI < 0) ? 2 : 4) void gemm256_k
     PPT_PRIO(p.wave_prio);
     const int wm = w / WGN, wn = w % WGN;
     const int nwg = gridDim.x * gridDim.y;
-    const int lin0 = blockIdx.y * gridDim.x + blockIdx.x;
-    const int q8 = nwg / 8, r8 = nwg % 8, xcd = lin0 % 8;                   // same XCD-aware remap as gemm_kernel
-    const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + lin0 / 8;
-    // ... and inside an XCD's run of tiles, GROUPS of GM tile rows are walked column-major: the ~32 tiles an XCD works on at one
-    // time then cover GM row panels x 32 / GM column panels instead of 1 x 32, so every operand slab is pulled over the fabric
-    // once per GM (A) resp. 32 / GM (B) tiles instead of A once per 32 and B once per TILE -- what matters when B does not fit the
-    // 4 MiB L2 (8192^3: 33 -> 12 panel streams per 32 tiles); for the tower's N <= 1536 it changes nothing measurable.
-    int tm, tn;
-    {
-        constexpr int GM = 4;
-        const int ncol = gridDim.x, nrow = gridDim.y;
-        const int grp = lin / (GM * ncol), first = grp * GM;
-        const int rows_here = min(GM, nrow - first);
-        const int t = lin - grp * GM * ncol;
-        tm = first + t % rows_here;
-        tn = t / rows_here;
-    }
+    int tm, tn;                                            // XCD-aware remap, then groups of four tile rows (gemm_common.h)
+    grouped_tile<4>(xcd_tile(blockIdx.y * gridDim.x + blockIdx.x, nwg), gridDim.x, gridDim.y, tm, tn);
     const int n0 = tn * BN, m0 = tm * BM;
     const T *A = reinterpret_cast<const T *>(p.A) + (int64_t)blockIdx.z * p.strideA;
     const T *B = reinterpret_cast<const T *>(p.B) + (int64_t)blockIdx.z * p.strideB;
 
     f32x16_t acc[TI][TJ];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    PPT_ZERO_ACC(acc, TI, TJ);
     const int nslab = p.K / BK, last = nslab - 1;
     auto issue = [&](int slab, int stage) {
-        glds_half8<T, BM>(A, p.lda, p.M, m0, slab * BK, smem + stage * STAGE, w, lane);
-        glds_half8<T, BN>(B, p.ldb, p.N, n0, slab * BK, smem + stage * STAGE + A_BYTES, w, lane);
+        glds_half<T, BM, 8>(A, p.lda, p.M, m0, slab * BK, smem + stage * STAGE, w, lane);
+        glds_half<T, BN, 8>(B, p.ldb, p.N, n0, slab * BK, smem + stage * STAGE + A_BYTES, w, lane);
     };
 #pragma unroll
     for (int i = 0; i < NSTAGE - 1; ++i) issue(min(i, last), i);
@@ -276,12 +204,13 @@ __global__ __launch_bounds__(NT2, (BN == 256 || EPI < 0) ? 2 : 4) void gemm256_k
     epilogue_prefetch<TI, TJ, (EPI < 0 || (EPI & EPI_GROUP) != 0)>(p, epre, lane, m0 + wm * WM, n0 + wn * WN);
     G256_STAMP(1);
     int stage = 0;
-    if constexpr (PP) {
+    if constexpr (BN == 256) {
         // STAGGERED schedule (round 5, v2): a wave alternates LOAD(s) -- the stage's fragments into registers, the LDS-DMA of slab
         // s + 3, the counted wait -- and COMPUTE(s) -- 16 MFMAs on registers -- with a workgroup barrier after each; waves 4-7 run
         // ONE SEGMENT BEHIND waves 0-3 (one extra barrier up front, one less at the end).  Every SIMD holds one wave of each
-        // half, so while one computes the other loads: the matrix pipe never waits for a barrier or an LDS read.  (v1 above lets
-        // all 8 waves meet at one barrier per stage and then issue DMA + reads together: measured 0.36 of peak at 8192^3.)
+        // half, so while one computes the other loads: the matrix pipe never waits for a barrier or an LDS read.  (Tried and
+        // removed for this tile: v1, the one-barrier loop below -- all 8 waves meet at one barrier per stage and then issue DMA +
+        // reads together: measured 0.36 of peak at 8192^3.)
         // Slab s is read in segments 2s (waves 0-3) and 2s + 1 (waves 4-7); its slot is refilled with slab s + 4, issued in
         // segments >= 2s + 2; a wave's wait at the end of LOAD(s) covers its pieces of slab s + 1, two segments before anyone
         // reads them.
@@ -309,16 +238,17 @@ __global__ __launch_bounds__(NT2, (BN == 256 || EPI < 0) ? 2 : 4) void gemm256_k
         }
         if (!late) __builtin_amdgcn_s_barrier();
     } else {
-    for (int s = 0; s < nslab; ++s) {
-        // own copies of slab s have landed (the LOADS * (NSTAGE - 2) youngest, slabs s+1 .., may still fly) ...
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(LOADS * (NSTAGE - 2)) : "memory");
-        __builtin_amdgcn_s_barrier();                     // ... and so have everybody else's: slab s is readable
-        if (s == 0) G256_STAMP(2);
-        int nstage = stage + NSTAGE - 1; if (nstage >= NSTAGE) nstage -= NSTAGE;
-        issue(min(s + NSTAGE - 1, last), nstage);         // that stage was last read at slab s-1, before this barrier
-        mma_half8<T, TI, TJ>(smem + stage * STAGE, smem + stage * STAGE + A_BYTES, wm * WM, wn * WN, lane, acc);
-        stage = stage + 1 == NSTAGE ? 0 : stage + 1;
-    }
+        // the 256 x 128 tile (two workgroups per CU cover each other's barriers): one barrier per stage
+        for (int s = 0; s < nslab; ++s) {
+            // own copies of slab s have landed (the LOADS * (NSTAGE - 2) youngest, slabs s+1 .., may still fly) ...
+            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(LOADS * (NSTAGE - 2)) : "memory");
+            __builtin_amdgcn_s_barrier();                     // ... and so have everybody else's: slab s is readable
+            if (s == 0) G256_STAMP(2);
+            int nstage = stage + NSTAGE - 1; if (nstage >= NSTAGE) nstage -= NSTAGE;
+            issue(min(s + NSTAGE - 1, last), nstage);         // that stage was last read at slab s-1, before this barrier
+            mma_half<T, TI, TJ, true>(smem + stage * STAGE, smem + stage * STAGE + A_BYTES, wm * WM, wn * WN, lane, acc);
+            stage = stage + 1 == NSTAGE ? 0 : stage + 1;
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // surplus prefetches must not land on the parked tile
     __builtin_amdgcn_s_barrier();
@@ -327,8 +257,8 @@ __global__ __launch_bounds__(NT2, (BN == 256 || EPI < 0) ? 2 : 4) void gemm256_k
     const int64_t zc = (int64_t)blockIdx.z * p.strideC;
     const int mw = m0 + wm * WM, nw = n0 + wn * WN;
     if constexpr (EPI >= 0) {
-        if constexpr (SLICED_EPILOGUE) epilogue_regs_sliced<TI, TJ, EPI>(p, acc, epre, smem + w * (32 * WN * 2), lane, mw, nw, zc);
-        else epilogue_regs<TI, TJ, EPI, 1>(p, acc, epre, smem + w * (WM * WN * 2), lane, mw, nw, zc);
+        // (Tried and removed: epilogue_regs on the whole wave tile -- with one workgroup per CU nothing covers its store tail.)
+        epilogue_regs_sliced<TI, TJ, EPI>(p, acc, epre, smem + w * (32 * WN * 2), lane, mw, nw, zc);
     } else {
         // row-major fp32 operands (residual stream, saved pre-activation, second output): the LDS walk, PR rows of the wave tile
         // at a time (an fp32 park of the whole 128 x 64 wave tile would be 256 KiB per workgroup)
@@ -354,13 +284,7 @@ __global__ __launch_bounds__(NT2, (BN == 256 || EPI < 0) ? 2 : 4) void gemm256_k
 
 extern "C" int ppt_get_gemm256(void);
 
-int env_int(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
-template <typename T, bool PPV>
+template <typename T>
 int launch256(const ppt_gemm_params &p, int bn, hipStream_t s)
 {
     const int batch = p.batch > 0 ? p.batch : 1;
@@ -372,16 +296,16 @@ int launch256(const ppt_gemm_params &p, int bn, hipStream_t s)
     if (epi != 0 && epi != EPI_GELU && !(bn == 256 && epi == (EPI_GROUP | EPI_STATS))) epi = -1;
     if (bn == 256) {
         switch (epi) {
-        case 0: hipLaunchKernelGGL((gemm256_kernel<T, 256, 4, 0, PPV>), grid, dim3(NT2), 0, s, p); break;
-        case EPI_GELU: hipLaunchKernelGGL((gemm256_kernel<T, 256, 4, EPI_GELU, PPV>), grid, dim3(NT2), 0, s, p); break;
-        case EPI_GROUP | EPI_STATS: hipLaunchKernelGGL((gemm256_kernel<T, 256, 4, EPI_GROUP | EPI_STATS, PPV>), grid, dim3(NT2), 0, s, p); break;
-        default: hipLaunchKernelGGL((gemm256_kernel<T, 256, 4, -1, PPV>), grid, dim3(NT2), 0, s, p); break;
+        case 0: hipLaunchKernelGGL((gemm256_kernel<T, 256, 4, 0>), grid, dim3(NT2), 0, s, p); break;
+        case EPI_GELU: hipLaunchKernelGGL((gemm256_kernel<T, 256, 4, EPI_GELU>), grid, dim3(NT2), 0, s, p); break;
+        case EPI_GROUP | EPI_STATS: hipLaunchKernelGGL((gemm256_kernel<T, 256, 4, EPI_GROUP | EPI_STATS>), grid, dim3(NT2), 0, s, p); break;
+        default: hipLaunchKernelGGL((gemm256_kernel<T, 256, 4, -1>), grid, dim3(NT2), 0, s, p); break;
         }
     } else {
         switch (epi) {
-        case 0: hipLaunchKernelGGL((gemm256_kernel<T, 128, 3, 0, false>), grid, dim3(NT2), 0, s, p); break;
-        case EPI_GELU: hipLaunchKernelGGL((gemm256_kernel<T, 128, 3, EPI_GELU, false>), grid, dim3(NT2), 0, s, p); break;
-        default: hipLaunchKernelGGL((gemm256_kernel<T, 128, 3, -1, false>), grid, dim3(NT2), 0, s, p); break;
+        case 0: hipLaunchKernelGGL((gemm256_kernel<T, 128, 3, 0>), grid, dim3(NT2), 0, s, p); break;
+        case EPI_GELU: hipLaunchKernelGGL((gemm256_kernel<T, 128, 3, EPI_GELU>), grid, dim3(NT2), 0, s, p); break;
+        default: hipLaunchKernelGGL((gemm256_kernel<T, 128, 3, -1>), grid, dim3(NT2), 0, s, p); break;
         }
     }
     PPT_CHECK_LAUNCH();
@@ -471,9 +395,9 @@ __global__ __launch_bounds__(NT2, 2) void gemm256s_kernel(const ppt_gemm_params 
     PPT_PRIO(p.wave_prio);
     const int wm = w / WGN, wn = w % WGN;
     const int nwg = gridDim.x * gridDim.y;
-    const int lin0 = blockIdx.y * gridDim.x + blockIdx.x;
-    const int q8 = nwg / 8, r8 = nwg % 8, xcd = lin0 % 8;                   // XCD-aware remap + grouped tile order (gemm256_kernel)
-    const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + lin0 / 8;
+    const int lin = xcd_tile(blockIdx.y * gridDim.x + blockIdx.x, nwg);
+    // gemm_common.h's grouped_tile<4>, written out: through the helper this kernel's prologue is scheduled differently
+    // (tools/kernel_isa_diff.py), and the kernels here are kept instruction for instruction
     int tm, tn;
     {
         constexpr int GM = 4;
@@ -490,12 +414,7 @@ __global__ __launch_bounds__(NT2, 2) void gemm256s_kernel(const ppt_gemm_params 
     const float sa = pow2f(p.split_a_pow2), sb = pow2f(p.split_b_pow2);
 
     f32x16_t acc[TI][TJ];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    PPT_ZERO_ACC(acc, TI, TJ);
     uint32_t split_over = 0;
     split256_loop<BM, BN, TI, TJ>(p, A, B, m0, n0, smem, wm * WM, wn * WN, lane, acc, sa, sb, split_over);
     scale_acc<TI, TJ>(acc, pow2f(-(p.split_a_pow2 + p.split_b_pow2)));
@@ -520,15 +439,7 @@ extern "C" int ppt_gemm256_split_dispatch(const ppt_gemm_params *pp, void *strea
     if (!enabled || p.dtype != PPT_F32 || !p.split16 || p.split16 == 2) return PPT_EUNSUPPORTED;      // (2: the caller asks for the tile loops)
     if (p.a_mode != PPT_A_PLAIN || !p.A || (p.K % 32) != 0 || p.K < 96) return PPT_EUNSUPPORTED;
     if (p.pool_max || p.col_sum || p.group_add) return PPT_EUNSUPPORTED;     // (the LDS-walk epilogue: no statistics, no pools)
-    bool ok = (p.N % 8) == 0;
-    if (p.C) ok = ok && (p.ldc % 8) == 0 && al16(p.C);
-    if (p.C2) ok = ok && (p.ldc2 % 8) == 0 && al16(p.C2);
-    if (p.bias) ok = ok && al16(p.bias);
-    if (p.dact_pre) ok = ok && (p.ld_dact % 8) == 0 && al16(p.dact_pre);
-    if (p.residual) ok = ok && (p.ld_res % 8) == 0 && al16(p.residual);
-    if (p.residual2) ok = ok && (p.ld_res2 % 8) == 0 && al16(p.residual2);
-    if (p.batch > 1 && ((p.strideC % 8) != 0)) ok = false;
-    if (!ok) return PPT_EUNSUPPORTED;
+    if (!vec_epilogue_ok(p, 0) || (p.batch > 1 && (p.strideC % 8) != 0)) return PPT_EUNSUPPORTED;
     dim3 grid((p.N + 127) / 128, (p.M + 255) / 256, p.batch > 0 ? p.batch : 1);
     if ((int64_t)grid.x * grid.y * grid.z < min_tiles || grid.y > 65535 || grid.z > 65535) return PPT_EUNSUPPORTED;
     hipLaunchKernelGGL((gemm256s_kernel<128>), grid, dim3(NT2), 0, ppt_stream(stream), p);
@@ -554,15 +465,7 @@ extern "C" int ppt_gemm256_dispatch(const ppt_gemm_params *pp, int force, void *
     const bool special = mask == 0 || mask == EPI_GELU || (bn == 256 && mask == (EPI_GROUP | EPI_STATS));
     if (!special) {                                       // the LDS-walk epilogue: 16-byte friendly operands only, no statistics
         if (p.col_sum || p.group_add) return PPT_EUNSUPPORTED;
-        bool ok = (p.N % 8) == 0;
-        if (p.C) ok = ok && (p.ldc % 8) == 0 && al16(p.C);
-        if (p.C2) ok = ok && (p.ldc2 % 8) == 0 && al16(p.C2);
-        if (p.bias) ok = ok && al16(p.bias);
-        if (p.dact_pre) ok = ok && (p.ld_dact % 8) == 0 && al16(p.dact_pre);
-        if (p.residual) ok = ok && (p.ld_res % 8) == 0 && al16(p.residual);
-        if (p.residual2) ok = ok && (p.ld_res2 % 8) == 0 && al16(p.residual2);
-        if (p.batch > 1 && ((p.strideC % 8) != 0)) ok = false;
-        if (!ok) return PPT_EUNSUPPORTED;
+        if (!vec_epilogue_ok(p, 0) || (p.batch > 1 && (p.strideC % 8) != 0)) return PPT_EUNSUPPORTED;
     }
     static const int enabled = env_int("PPT_GEMM256", 1);
     static const int min_rows = env_int("PPT_GEMM256_MIN_ROWS", 8192);
@@ -580,9 +483,7 @@ extern "C" int ppt_gemm256_dispatch(const ppt_gemm_params *pp, int force, void *
         if (p.K < long_k && !(p.act == PPT_ACT_NONE && tiles >= 512)) return PPT_EUNSUPPORTED;
     }
     hipStream_t s = ppt_stream(stream);
-    static const int stagger = env_int("PPT_GEMM256_PP", 1);         // the staggered schedule (0: one barrier per stage, v1)
-    if (stagger) return p.dtype == PPT_BF16 ? launch256<bf16_t, true>(p, bn, s) : launch256<f16_t, true>(p, bn, s);
-    return p.dtype == PPT_BF16 ? launch256<bf16_t, false>(p, bn, s) : launch256<f16_t, false>(p, bn, s);
+    return p.dtype == PPT_BF16 ? launch256<bf16_t>(p, bn, s) : launch256<f16_t>(p, bn, s);
 }
 
 extern "C" int ppt_gemm256(const ppt_gemm_params *pp, void *stream)
@@ -590,11 +491,9 @@ extern "C" int ppt_gemm256(const ppt_gemm_params *pp, void *stream)
     if (!pp) return PPT_EINVAL;
     ppt_gemm_params q = *pp;
     if (!q.wave_prio) q.wave_prio = ppt_get_wave_priority();
-    if (q.M <= 0 || q.N <= 0 || q.K <= 0 || !q.B || !q.A) return PPT_EINVAL;
-    if (q.K % 8 || q.lda % 8 || q.ldb % 8 || ((uintptr_t)q.A & 15) || ((uintptr_t)q.B & 15)) return PPT_EINVAL;
+    if (const int rc = validate_dims(q)) return rc;
+    if (!q.A || q.K % 8 || q.lda % 8 || q.ldb % 8 || ((uintptr_t)q.A & 15) || ((uintptr_t)q.B & 15)) return PPT_EINVAL;
     if ((q.col_sum == nullptr) != (q.col_sqsum == nullptr)) return PPT_EINVAL;
-    if (q.group_add && q.group_rows <= 0) return PPT_EINVAL;
-    if (q.row_scale && q.row_scale_rows <= 0) return PPT_EINVAL;
-    if (q.batch > 1 && (q.C2 || q.col_sum || q.pool_max || q.residual || q.residual2 || q.dact_pre || q.group_add)) return PPT_EUNSUPPORTED;
+    if (const int rc = validate_operands(q)) return rc;
     return ppt_gemm256_dispatch(&q, 1, stream);
 }

@@ -1,6 +1,8 @@
-// gemm_common.h -- what the tile GEMM kernels of gemm.hip and gemm256.hip share: the XOR-swizzled LDS image, the activation
-// helpers, the A-prologue loaders of the register-staged kernel and the three epilogues (scalar, 16-byte LDS walk, register
-// layout).  Internal linkage on purpose: every translation unit gets its own copy.
+// gemm_common.h -- what the tile GEMM kernels of gemm.hip and gemm256.hip share: the two XOR-swizzled LDS images (128-byte and
+// 64-byte rows), the tile order (XCD remap, grouped walk), the LDS-DMA fill and the MFMA step of the half-slab loops, the
+// activation helpers, the A-prologue loaders of the register-staged kernel, the accumulator zero-fill and fp32 park, the three
+// epilogues (scalar, 16-byte LDS walk, register layout) and the host-side argument checks of the two entry points.  Internal
+// linkage on purpose: every translation unit gets its own copy.
 #pragma once
 #include <stdlib.h>
 #include "ppt_common.h"
@@ -11,10 +13,35 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
-constexpr int ROWB = 128, NT = 256;
-
+constexpr int ROWB = 128, ROWH = 64, NT = 256;
 
 __device__ __forceinline__ int lds_off(int row, int chunk) { return row * ROWB + ((chunk ^ ((row >> 1) & 7)) << 4); }
+// the 64-byte-row image (half-slab LDS-DMA loops, split16 hi / lo images): 16-byte chunk c of row r at slot c ^ ((r >> 2) & 3) --
+// four consecutive rows fill one 256-byte bank row, and the lane groups of ds_read_b128 ({0-3,12-15,20-27}, ...) touch 16 distinct slots
+__device__ __forceinline__ int lds_off_h(int row, int chunk) { return row * ROWH + ((chunk ^ ((row >> 2) & 3)) << 4); }
+
+// ---- tile order ---------------------------------------------------------------------------------
+// consecutive tiles (same m-tile, n fastest) onto one XCD: blocks are dealt round-robin over the 8 XCDs, each with a private
+// L2, so without this remap the column tiles that share one A row panel land on 8 different L2s (measured +5..8 % on the
+// block GEMMs; speed only, never correctness).  lin0: the block's linear index, nwg: blocks per batch slice.
+__device__ __forceinline__ int xcd_tile(int lin0, int nwg)
+{
+    const int q8 = nwg / 8, r8 = nwg % 8, xcd = lin0 % 8;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + lin0 / 8;
+}
+// ... and inside an XCD's run of tiles, GROUPS of GM tile rows are walked column-major: the ~32 tiles an XCD works on at one
+// time then cover GM row panels x 32 / GM column panels instead of 1 x 32, so every operand slab is pulled over the fabric
+// once per GM (A) resp. 32 / GM (B) tiles instead of A once per 32 and B once per TILE -- what matters when B does not fit the
+// 4 MiB L2 (8192^3: 33 -> 12 panel streams per 32 tiles); for the tower's N <= 1536 it changes nothing measurable.
+template <int GM>
+__device__ __forceinline__ void grouped_tile(int lin, int ncol, int nrow, int &tm, int &tn)
+{
+    const int grp = lin / (GM * ncol), first = grp * GM;
+    const int rows_here = min(GM, nrow - first);
+    const int t = lin - grp * GM * ncol;
+    tm = first + t % rows_here;
+    tn = t / rows_here;
+}
 
 template <bool FAST>
 __device__ __forceinline__ float act_fwd(float v, int act)
@@ -288,6 +315,105 @@ __device__ __forceinline__ void mma_slab(const unsigned char *As, const unsigned
     }
 }
 
+// ---- the half-slab LDS-DMA loops (gemm_kernel_glds_h, gemm256_kernel): 64-byte K slabs in the lds_off_h image -------------------
+// ROWS x 64 bytes of an operand -> LDS, by the NW waves of the workgroup: ROWS / (16 NW) pieces of 1 KiB (16 rows) per wave.  The
+// DMA writes 64 lanes x 16 B linearly, so the swizzle is applied to each lane's SOURCE chunk (same involution as the fragment reads).
+template <typename T, int ROWS, int NW>
+__device__ __forceinline__ void glds_half(const T *base, int64_t ld, int rows, int r0, int k0, unsigned char *tile, int w, int lane)
+{
+    constexpr int EPC = 16 / sizeof(T);
+    constexpr int PER_WAVE = ROWS / (16 * NW);
+#pragma unroll
+    for (int i = 0; i < PER_WAVE; ++i) {
+        const int rg = (w * PER_WAVE + i) * 16;
+        const int r = rg + (lane >> 2);
+        const int c = (lane & 3) ^ ((r >> 2) & 3);       // source chunk that belongs in LDS slot lane&3 of row r
+        const T *src = base + (int64_t)min(r0 + r, rows - 1) * ld + k0 + c * EPC;
+        lds_dma16(src, tile + rg * ROWH);
+    }
+}
+
+// one 64-byte K slab of MFMAs for this wave's (32*TI) x (32*TJ).  B_FIRST: the 16-bit fragments of B are read before those of A
+// (gemm256_kernel; gemm_kernel_glds_h reads A first) -- the same reads and MFMAs either way, but the order reaches the schedule.
+template <typename T, int TI, int TJ, bool B_FIRST = false>
+__device__ __forceinline__ void mma_half(const unsigned char *As, const unsigned char *Bs, int arow0, int brow0, int lane,
+                                         f32x16_t (&acc)[TI][TJ])
+{
+    const int r = lane & 31, h = lane >> 5;
+    if constexpr (sizeof(T) == 2) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            uint4 a[TI], b[TJ];
+            if constexpr (B_FIRST) {
+#pragma unroll
+                for (int j = 0; j < TJ; ++j)
+                    b[j] = *reinterpret_cast<const uint4 *>(Bs + lds_off_h(brow0 + j * 32 + r, kk * 2 + h));
+            }
+#pragma unroll
+            for (int i = 0; i < TI; ++i)
+                a[i] = *reinterpret_cast<const uint4 *>(As + lds_off_h(arow0 + i * 32 + r, kk * 2 + h));
+            if constexpr (!B_FIRST) {
+#pragma unroll
+                for (int j = 0; j < TJ; ++j)
+                    b[j] = *reinterpret_cast<const uint4 *>(Bs + lds_off_h(brow0 + j * 32 + r, kk * 2 + h));
+            }
+#pragma unroll
+            for (int i = 0; i < TI; ++i)
+#pragma unroll
+                for (int j = 0; j < TJ; ++j)
+                    acc[i][j] = h16<T>::mfma32(a[i], b[j], acc[i][j]);
+        }
+    } else {                                // (fp32 parity mode: gemm_kernel_glds_h<float> only)
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) {
+            const int kq = 2 * kk + h;      // k index (in floats) inside the 16-float slab
+            float a[TI], b[TJ];
+#pragma unroll
+            for (int i = 0; i < TI; ++i)
+                a[i] = *reinterpret_cast<const float *>(As + lds_off_h(arow0 + i * 32 + r, kq >> 2) + (kq & 3) * 4);
+#pragma unroll
+            for (int j = 0; j < TJ; ++j)
+                b[j] = *reinterpret_cast<const float *>(Bs + lds_off_h(brow0 + j * 32 + r, kq >> 2) + (kq & 3) * 4);
+#pragma unroll
+            for (int i = 0; i < TI; ++i)
+#pragma unroll
+                for (int j = 0; j < TJ; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
+    }
+}
+
+// ---- accumulators -------------------------------------------------------------------------------
+// These two are MACROS on purpose.  The compiler optimises a function on its own before it inlines it (always_inline included),
+// so a helper that loops over the accumulator array reaches the kernel already unrolled; the array is then promoted to registers
+// one pass earlier than with the loop written in the kernel, the kernel's values come out in another order, and scheduling and
+// register allocation of the whole K loop shift (tools/kernel_isa_diff.py: every kernel of gemm.hip and gemm256.hip differed).
+// As text pasted into the kernel they compile to what the written-out loops compiled to.  A brace block (used as a statement,
+// with its semicolon), not do { } while (0), for the same reason; the names inside carry a prefix so that no argument captures one.
+// zero a wave's accumulators, f32x16_t acc[TI][TJ]
+#define PPT_ZERO_ACC(acc, TI, TJ)                                                                                   \
+    {                                                                                                               \
+        _Pragma("unroll") for (int za_i = 0; za_i < (TI); ++za_i)                                                   \
+            _Pragma("unroll") for (int za_j = 0; za_j < (TJ); ++za_j)                                               \
+                _Pragma("unroll") for (int za_r = 0; za_r < 16; ++za_r) (acc)[za_i][za_j][za_r] = 0.0f;             \
+    }
+// MFMA tile rows [I0, I0 + NI) of a wave's accumulators -> the wave's own slice of LDS, row-major fp32 (NI * 32 rows of TJ * 32
+// floats), readable by the whole wave afterwards.  That turns the MFMA C layout (column on the lane, rows scattered over 16
+// registers) into the rows that epilogue_vec8 / epilogue_scalar walk.  (I0 a constant expression: a runtime index into the
+// accumulator array would send it to scratch.)
+#define PPT_PARK_F32(acc, ct, lane, I0, NI, TJ)                                                                     \
+    {                                                                                                               \
+        const int pk_h = (lane) >> 5, pk_cl = (lane) & 31;                                                          \
+        _Pragma("unroll") for (int pk_i = 0; pk_i < (NI); ++pk_i)                                                   \
+            _Pragma("unroll") for (int pk_j = 0; pk_j < (TJ); ++pk_j)                                               \
+                _Pragma("unroll") for (int pk_r = 0; pk_r < 16; ++pk_r)                                             \
+                    (ct)[(pk_i * 32 + (pk_r & 3) + 8 * (pk_r >> 2) + 4 * pk_h) * ((TJ) * 32) + pk_j * 32 + pk_cl] = \
+                        (acc)[(I0) + pk_i][pk_j][pk_r];                                                             \
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                      \
+        __builtin_amdgcn_wave_barrier();                                                                            \
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                                                      \
+    }
+
 // ---- split16: fp32 operands multiplied as hi + lo IEEE-half pairs on the 16-bit matrix pipe (ppt_gemm_params.split16) --------
 // x * s = hi + lo with hi = half(x * s), lo = half(x * s - hi): 22 significand bits while |x * s| >= 2^-2, an absolute floor of
 // 2^-25 below (half's subnormal step), inf above 65 504 -- s is the caller's power of two (split_a_pow2 / split_b_pow2).
@@ -301,7 +427,6 @@ __device__ __forceinline__ void mma_slab(const unsigned char *As, const unsigned
 // (First version, measured and replaced: splitting at fragment-read time out of the fp32 LDS image -- every wave of a 2 x 2
 // workgroup splits both operands again, 96 VALU instructions per 6 MFMAs: 1.3-1.5x the fp32 MFMA, tools/split16_bench.py.)
 typedef _Float16 ppt_h2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int lds_off_s(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
 __device__ __forceinline__ float pow2f(int e) { return __uint_as_float((uint32_t)(127 + e) << 23); }
 
 // Range (round 6): half(x * s) is inf beyond 65 504 and lo = half(x * s - inf) is NaN, where the fp32 MFMA this mode
@@ -352,7 +477,7 @@ __device__ __forceinline__ void write_stage_split(const Stage<NR> &st, unsigned 
             H[q] = __builtin_bit_cast(uint32_t, hh);
             L[q] = __builtin_bit_cast(uint32_t, ll);
         }
-        const int off = lds_off_s(row, ch >> 1) + (ch & 1) * 8;
+        const int off = lds_off_h(row, ch >> 1) + (ch & 1) * 8;
         *reinterpret_cast<uint2 *>(tile + off) = make_uint2(H[0], H[1]);
         *reinterpret_cast<uint2 *>(tile + ROWS * 64 + off) = make_uint2(L[0], L[1]);
     }
@@ -374,13 +499,13 @@ __device__ __forceinline__ void mma_slab_split(const unsigned char *As, const un
         uint4 ah[TI], al[TI], bh[TJ], bl[TJ];
 #pragma unroll
         for (int i = 0; i < TI; ++i) {
-            const unsigned char *q = As + lds_off_s(arow0 + i * 32 + r, kk * 2 + h);
+            const unsigned char *q = As + lds_off_h(arow0 + i * 32 + r, kk * 2 + h);
             ah[i] = *reinterpret_cast<const uint4 *>(q);
             al[i] = *reinterpret_cast<const uint4 *>(q + AROWS * 64);
         }
 #pragma unroll
         for (int j = 0; j < TJ; ++j) {
-            const unsigned char *q = Bs + lds_off_s(brow0 + j * 32 + r, kk * 2 + h);
+            const unsigned char *q = Bs + lds_off_h(brow0 + j * 32 + r, kk * 2 + h);
             bh[j] = *reinterpret_cast<const uint4 *>(q);
             bl[j] = *reinterpret_cast<const uint4 *>(q + BROWS * 64);
         }
@@ -661,8 +786,9 @@ __device__ __forceinline__ void epilogue_vec8(const ppt_gemm_params &p, float *c
 
 __host__ __device__ __forceinline__ bool al16(const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
-// wave-uniform: every pointer / leading dimension the vector epilogue touches is 16-byte friendly
-__device__ __forceinline__ bool vec_epilogue_ok(const ppt_gemm_params &p, int64_t zc)
+// wave-uniform: every pointer / leading dimension the vector epilogue touches is 16-byte friendly (the 256-row dispatchers ask
+// the same question on the host, with zc = 0 and their own strideC test)
+__host__ __device__ __forceinline__ bool vec_epilogue_ok(const ppt_gemm_params &p, int64_t zc)
 {
     bool ok = (p.N % 8) == 0;
     if (p.C) ok = ok && (p.ldc % 8) == 0 && (zc % 8) == 0 && al16(p.C);
@@ -898,6 +1024,29 @@ __device__ __forceinline__ void epilogue_regs(const ppt_gemm_params &p, f32x16_t
         const uint4 d = *reinterpret_cast<const uint4 *>(park + row * ROWBYTES + ((ch * 16) ^ (TJ == 2 ? (row & 1) << 6 : 0)));
         if (m < p.M && n < p.N) *reinterpret_cast<uint4 *>(C + (int64_t)m * p.ldc + n) = d;
     }
+}
+
+// ---- host side ----------------------------------------------------------------------------------
+int env_int(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+// the argument checks ppt_gemm and ppt_gemm256 share, as the two runs of them that each entry point makes at its old places: the
+// first before, the second after its own checks (dtype, alignment, prologue, statistics and pooling operands), so that a call
+// with two bad arguments is answered with the code it always got
+static int validate_dims(const ppt_gemm_params &p)
+{
+    return (p.M <= 0 || p.N <= 0 || p.K <= 0 || !p.B) ? PPT_EINVAL : PPT_OK;
+}
+static int validate_operands(const ppt_gemm_params &p)
+{
+    if (p.group_add && p.group_rows <= 0) return PPT_EINVAL;
+    if (p.row_scale && p.row_scale_rows <= 0) return PPT_EINVAL;
+    if (p.batch > 1 && (p.C2 || p.col_sum || p.pool_max || p.residual || p.residual2 || p.dact_pre || p.group_add))
+        return PPT_EUNSUPPORTED;
+    return PPT_OK;
 }
 
 }  // namespace
