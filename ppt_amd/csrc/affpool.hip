@@ -9,12 +9,9 @@
 // its row) straight from y1 and applies the affine in registers (constants from a 1 KB LDS table), one group of 32 rows
 // per MFMA tile, no staging, no barrier; the epilogue is register-only.  Same expression and summation order as the generic
 // prologue / MFMA loop: maxima and minima are bit-identical to that path.
-#include "ppt_common.h"
+#include "group_tile.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
 template <int KS, int TJ, int NWN, int PR>
 __global__ __launch_bounds__(256) void affpool_kernel(const bf16_t *__restrict__ A, int64_t lda, int n_units,
@@ -31,13 +28,11 @@ __global__ __launch_bounds__(256) void affpool_kernel(const bf16_t *__restrict__
     for (int c = threadIdx.x; c < K; c += 256) tab[c] = make_float2(a_scale[c], a_shift[c]);
     const int col = lane & 31, h = lane >> 5;
     const int n_w = 32 * TJ * wn;
-    bf16x8_t bfrag[TJ][KS];
+    uint4 bfrag[TJ][KS];
     float bias[TJ];
 #pragma unroll
     for (int j = 0; j < TJ; ++j) {
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-            bfrag[j][s] = *reinterpret_cast<const bf16x8_t *>(W + (size_t)(n_w + 32 * j + col) * K + 16 * s + 8 * h);
+        PPT_GT_LOAD_WEIGHTS(bfrag[j], KS, W, n_w + 32 * j + col, h);
         bias[j] = bias_p ? bias_p[n_w + 32 * j + col] : 0.f;
     }
     __syncthreads();
@@ -53,7 +48,7 @@ __global__ __launch_bounds__(256) void affpool_kernel(const bf16_t *__restrict__
             uint4 araw[KS];
 #pragma unroll
             for (int s = 0; s < KS; ++s) araw[s] = *reinterpret_cast<const uint4 *>(ap + 16 * s);
-            f32x16_t acc[TJ];
+            ppt_f32x16 acc[TJ];
 #pragma unroll
             for (int j = 0; j < TJ; ++j)
 #pragma unroll
@@ -66,13 +61,11 @@ __global__ __launch_bounds__(256) void affpool_kernel(const bf16_t *__restrict__
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const float4 c2 = tp[i];                                                 // sc[2i], sh[2i], sc[2i+1], sh[2i+1]
-                    const float lo = fmaxf(fmaf(__uint_as_float(wv[i] << 16), c2.x, c2.y), 0.0f);
-                    const float hi = fmaxf(fmaf(__uint_as_float(wv[i] & 0xFFFF0000u), c2.z, c2.w), 0.0f);
-                    pk[i] = pack_bf16x2(lo, hi);
+                    pk[i] = affine_relu_pair16<bf16_t>(wv[i], c2.x, c2.y, c2.z, c2.w);
                 }
-                const bf16x8_t a = __builtin_bit_cast(bf16x8_t, make_uint4(pk[0], pk[1], pk[2], pk[3]));
+                const uint4 a = make_uint4(pk[0], pk[1], pk[2], pk[3]);
 #pragma unroll
-                for (int j = 0; j < TJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bfrag[j][s], acc[j], 0, 0, 0);
+                for (int j = 0; j < TJ; ++j) acc[j] = h16<bf16_t>::mfma32(a, bfrag[j][s], acc[j]);
             }
             // C layout: column (lane & 31), rows (e & 3) + 8 (e >> 2) + 4 h: e < 8 are rows 0-15, e >= 8 rows 16-31
 #pragma unroll
@@ -86,16 +79,7 @@ __global__ __launch_bounds__(256) void affpool_kernel(const bf16_t *__restrict__
                     if (e < 8) { m0 = fmaxf(m0, acc[j][e]); l0 = fminf(l0, acc[j][e]); }
                     else { m1 = fmaxf(m1, acc[j][e]); l1 = fminf(l1, acc[j][e]); }
                 }
-                sm = xor32_sum(sm);
-                const float mean = sm * (1.0f / 32.0f);
-                float q = 0.f;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) { const float d = acc[j][e] - mean; q = fmaf(d, d, q); }
-                q = xor32_sum(q);
-                if (h == 0) {
-                    part_sum[t * N + n] = sm;
-                    part_m2[t * N + n] = q;
-                }
+                PPT_GT_CHUNK_STATS(acc[j], sm, h, part_sum, part_m2, t * N + n);
                 if constexpr (PR == 16) {
                     m0 = xor32_max(m0); m1 = xor32_max(m1); l0 = xor32_min(l0); l1 = xor32_min(l1);
                     if (h == 0) {

@@ -151,19 +151,8 @@ __device__ __forceinline__ void mask_plain(Stage<NR> &st, int rows, int K, int r
     }
 }
 
+// (the 16-bit forms: ppt_common.h's affine_relu_chunk16)
 template <typename T> __device__ __forceinline__ void affine_relu_chunk(uint4 &v, const float *sc, const float *sh);
-template <typename T>
-__device__ __forceinline__ void affine_relu_chunk16(uint4 &v, const float *sc, const float *sh)
-{
-    uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float lo = fmaxf(fmaf(h16<T>::lo(w[e]), sc[2 * e], sh[2 * e]), 0.0f);
-        const float hi = fmaxf(fmaf(h16<T>::hi(w[e]), sc[2 * e + 1], sh[2 * e + 1]), 0.0f);
-        w[e] = h16<T>::pack2(lo, hi);
-    }
-    v = make_uint4(w[0], w[1], w[2], w[3]);
-}
 template <> __device__ __forceinline__ void affine_relu_chunk<bf16_t>(uint4 &v, const float *sc, const float *sh) { affine_relu_chunk16<bf16_t>(v, sc, sh); }
 template <> __device__ __forceinline__ void affine_relu_chunk<f16_t>(uint4 &v, const float *sc, const float *sh) { affine_relu_chunk16<f16_t>(v, sc, sh); }
 template <>

@@ -12,11 +12,9 @@
 //     LDS transpose so that rows leave as 128-byte pieces.
 // Bound: the y2 write (512 B per point, ~70 us at 4 TB/s); the A fragments are recomputed by the four waves of a group
 // (VALU ~45 us per SIMD), which is what buys the absence of any barrier.
-#include "ppt_common.h"
+#include "group_tile.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
 // C1: channels of the K=3 conv (= K of the MFMA product); a wave owns TJ column tiles of 32; NWN waves side by side cover
 // N = 32 * TJ * NWN columns, the 4 / NWN wave rows of a workgroup take different groups of 32 points.
@@ -47,9 +45,7 @@ __global__ __launch_bounds__(256) void mpn1_kernel(const float *__restrict__ pts
     float bias[TJ];
 #pragma unroll
     for (int j = 0; j < TJ; ++j) {
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-            bfrag[j][s] = *reinterpret_cast<const uint4 *>(W2 + (size_t)(n_w + 32 * j + col) * C1 + 16 * s + 8 * h);
+        PPT_GT_LOAD_WEIGHTS(bfrag[j], KS, W2, n_w + 32 * j + col, h);
         bias[j] = bias2 ? bias2[n_w + 32 * j + col] : 0.f;
     }
     unsigned char *tr = tr_all[w];
@@ -58,7 +54,7 @@ __global__ __launch_bounds__(256) void mpn1_kernel(const float *__restrict__ pts
     for (int t = blockIdx.x * NWM + wm; t < n_tiles; t += gridDim.x * NWM) {
         const float *pp = pts + ((size_t)t * 32 + col) * 3;
         const float x = pp[0], y = pp[1], z = pp[2];
-        f32x16_t acc[TJ];
+        ppt_f32x16 acc[TJ];
 #pragma unroll
         for (int j = 0; j < TJ; ++j)
 #pragma unroll
@@ -91,57 +87,17 @@ __global__ __launch_bounds__(256) void mpn1_kernel(const float *__restrict__ pts
                 mx = xor32_max(mx);
                 if (h == 0) gmax[(size_t)t * N + n_w + 32 * j + col] = h16<F>::from_f32(mx);
             }
-            if constexpr (STATS) {
-                sm = xor32_sum(sm);
-                const float mean = sm * (1.0f / 32.0f);
-                float q = 0.f;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) { const float d = acc[j][e] - mean; q = fmaf(d, d, q); }
-                q = xor32_sum(q);
-                if (h == 0) {
-                    part_sum[(size_t)t * N + n_w + 32 * j + col] = sm;
-                    part_m2[(size_t)t * N + n_w + 32 * j + col] = q;
-                }
-            }
-            // neighbour lanes trade one value per register pair, so that a lane owns two adjacent columns of one row:
-            // even lanes keep row(e0), odd lanes row(e1) -- 4-byte LDS writes instead of 2-byte ones
-#pragma unroll
-            for (int q2 = 0; q2 < 8; ++q2) {
-                const int e0 = 2 * q2, e1 = 2 * q2 + 1;
-                const float send = (lane & 1) ? acc[j][e0] : acc[j][e1];
-                const float recv = __uint_as_float(dpp_mov<0xB1, 0xf>(__float_as_uint(send)));     // quad_perm [1,0,3,2]
-                const uint32_t packed = (lane & 1) ? h16<F>::pack2(recv, acc[j][e1]) : h16<F>::pack2(acc[j][e0], recv);
-                const int e = (lane & 1) ? e1 : e0;
-                const int row = (e & 3) + 8 * (e >> 2) + 4 * h;
-                *reinterpret_cast<uint32_t *>(tr + row * PITCH + (32 * j + (col & ~1)) * 2) = packed;
-            }
+            if constexpr (STATS) PPT_GT_CHUNK_STATS(acc[j], sm, h, part_sum, part_m2, (size_t)t * N + n_w + 32 * j + col);
+            PPT_GT_TILE_TO_LDS(F, acc[j], tr, PITCH, j, lane, col, h);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // rows leave as 64 TJ-byte pieces: 4 TJ lanes x 16 bytes per row
-        constexpr int LPR = 4 * TJ, RPI = 64 / LPR, NIT = (32 + RPI - 1) / RPI;      // lanes per row, rows per instruction
-#pragma unroll
-        for (int q2 = 0; q2 < NIT; ++q2) {
-            const int row = RPI * q2 + lane / LPR, ch = lane % LPR;
-            if (row < 32 && lane < RPI * LPR) {
-                const uint4 v = *reinterpret_cast<const uint4 *>(tr + row * PITCH + ch * 16);
-                ppt_store16_stream(y2 + ((size_t)t * 32 + row) * N + n_w + ch * 8, v);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        PPT_GT_TILE_OUT(TJ, tr, PITCH, y2, (size_t)t * 32, N, n_w, lane);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");          // (no workgroup barrier here: the next group's tile writes
+        __builtin_amdgcn_wave_barrier();                                //  stay behind these reads)
     }
 }
 
-int mpn1_grid(int64_t tiles, int nwm, hipStream_t st)
-{
-    const int cus = ppt_cu_count(st);            // (of the stream's device, not process-global state)
-    const int64_t blocks = (tiles + nwm - 1) / nwm;
-    int64_t want = (int64_t)cus * 3 * ppt_get_persistent_occupancy() / 100;        // (ppt_set_persistent_occupancy)
-    want = want < 8 ? 8 : want;
-    return (int)(blocks < want ? blocks : want);
-}
+// three persistent workgroups per CU; a workgroup takes `nwm` groups per step
+int mpn1_grid(int64_t tiles, int nwm, hipStream_t st) { return ppt_persistent_grid((tiles + nwm - 1) / nwm, 3, st); }
 
 }  // namespace
 
@@ -154,12 +110,11 @@ extern "C" int ppt_mini_pointnet_conv12_half(const float *pts, int64_t M, const 
     if (C1 != 128 || N != 256 || M % 32) return PPT_EUNSUPPORTED;
     if (((uintptr_t)W2 | (uintptr_t)y2) & 15) return PPT_EINVAL;
     const int64_t tiles = M / 32;
-    if (dtype == PPT_F16)
-        hipLaunchKernelGGL((mpn1_kernel<f16_t, 128, 2, 4, true, false>), dim3(mpn1_grid(tiles, 1, ppt_stream(stream))), dim3(256), 0, ppt_stream(stream), pts,
-                           (int)tiles, w1, b1, a_scale, a_shift, (const bf16_t *)W2, bias2, (bf16_t *)y2, (bf16_t *)gmax, nullptr, nullptr);
-    else
-        hipLaunchKernelGGL((mpn1_kernel<bf16_t, 128, 2, 4, true, false>), dim3(mpn1_grid(tiles, 1, ppt_stream(stream))), dim3(256), 0, ppt_stream(stream), pts,
-                           (int)tiles, w1, b1, a_scale, a_shift, (const bf16_t *)W2, bias2, (bf16_t *)y2, (bf16_t *)gmax, nullptr, nullptr);
+    ppt_launch16(dtype, [&](auto f) {
+        hipLaunchKernelGGL((mpn1_kernel<decltype(f), 128, 2, 4, true, false>), dim3(mpn1_grid(tiles, 1, ppt_stream(stream))), dim3(256), 0,
+                           ppt_stream(stream), pts, (int)tiles, w1, b1, a_scale, a_shift, (const bf16_t *)W2, bias2, (bf16_t *)y2, (bf16_t *)gmax,
+                           nullptr, nullptr);
+    });
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }

@@ -31,8 +31,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-
 constexpr int K1 = 256, N1 = 512, N2 = 256;                        // y2 width, y3 width, token width
 constexpr int R = 128, RS = 64;                                    // rows per chunk (four groups) / per phase-1 sub-chunk
 constexpr int KS1 = K1 / 16, KS2 = N1 / 16;                        // k-steps of the two products
@@ -111,7 +109,7 @@ __global__ __launch_bounds__(512, 2) void mpn34_kernel(const bf16_t *__restrict_
         }
     };
     // ---- phase 1 of one sub-chunk: MFMA loop over the y2 image at `ab`; returns with acc = W3s y2 + gs (pre-activation)
-    f32x16_t acc[2][2];
+    ppt_f32x16 acc[2][2];
     auto phase1 = [&](const unsigned char *ab, int g_first) {
         // group biases for this lane's two weight rows, requested in front of the loop that hides their latency
         const int g0 = min(g_first, n_tiles - 1), g1 = min(g_first + 1, n_tiles - 1);
@@ -207,7 +205,7 @@ __global__ __launch_bounds__(512, 2) void mpn34_kernel(const bf16_t *__restrict_
         if (chunk + (int)gridDim.x < n_chunks) request_a(chunk + (int)gridDim.x, 0, as);
 
         // ---- phase 2: acc2[rb] [m = 32 rb + (e & 3) + 8 (e >> 2) + 4 h][c = 32 w + ml], rb = the chunk's four groups
-        f32x16_t acc2[4];
+        ppt_f32x16 acc2[4];
 #pragma unroll
         for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
@@ -271,24 +269,13 @@ extern "C" int ppt_mini_pointnet_conv34_half(const void *y2, int64_t M, const vo
     if (!y2 || !W3s || !gs || !W4_tiled || !tok || M <= 0) return PPT_EINVAL;
     if (M % 32 || M / 32 > 0x3fffffff) return PPT_EUNSUPPORTED;
     if (((uintptr_t)y2 | (uintptr_t)W3s | (uintptr_t)W4_tiled) & 15) return PPT_EINVAL;
-    static const int attrs_once = [] {
-        (void)hipFuncSetAttribute((const void *)mpn34_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute((const void *)mpn34_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        return 0;
-    }();
-    (void)attrs_once;
-    const int cus = ppt_cu_count(ppt_stream(stream));            // (of the stream's device, not process-global state)
+    PPT_RAISE_LDS_ONCE(LDS_BYTES, (const void *)mpn34_kernel<bf16_t>, (const void *)mpn34_kernel<f16_t>);
     const int tiles = (int)(M / 32), chunks = (tiles + 3) / 4;
-    // one persistent workgroup per CU, fewer when the caller leaves room for the other stream (ppt_set_persistent_occupancy)
-    int64_t want = (int64_t)cus * ppt_get_persistent_occupancy() / 100;
-    want = want < 8 ? 8 : want;
-    const int grid = (int)(chunks < want ? chunks : want);
-    if (dtype == PPT_F16)
-        hipLaunchKernelGGL(mpn34_kernel<f16_t>, dim3(grid), dim3(512), LDS_BYTES, ppt_stream(stream), (const bf16_t *)y2, tiles, (const bf16_t *)W3s, gs,
-                           (const bf16_t *)W4_tiled, bias4, (bf16_t *)tok);
-    else
-        hipLaunchKernelGGL(mpn34_kernel<bf16_t>, dim3(grid), dim3(512), LDS_BYTES, ppt_stream(stream), (const bf16_t *)y2, tiles, (const bf16_t *)W3s, gs,
-                           (const bf16_t *)W4_tiled, bias4, (bf16_t *)tok);
+    const int grid = ppt_persistent_grid(chunks, 1, ppt_stream(stream));        // one persistent workgroup per CU
+    ppt_launch16(dtype, [&](auto f) {
+        hipLaunchKernelGGL(mpn34_kernel<decltype(f)>, dim3(grid), dim3(512), LDS_BYTES, ppt_stream(stream), (const bf16_t *)y2, tiles,
+                           (const bf16_t *)W3s, gs, (const bf16_t *)W4_tiled, bias4, (bf16_t *)tok);
+    });
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }

@@ -109,6 +109,25 @@ __device__ __forceinline__ float hi_dt(int code, uint32_t w) { return code == PP
 __device__ __forceinline__ uint16_t from_f32_dt(int code, float v) { return code == PPT_F16 ? f32_to_f16(v) : f32_to_bf16(v); }
 __device__ __forceinline__ float to_f32_dt(int code, uint16_t v) { return code == PPT_F16 ? f16_to_f32(v) : bf16_to_f32(v); }
 
+// Folded BatchNorm + ReLU on 16-bit values, rounded once: relu(sc * v + sh) on a packed pair, and on a 16-byte chunk of eight with
+// sc[e], sh[e] per value.  The one expression every A prologue of the library uses (gemm_common.h's affine_relu_chunk, the group
+// kernels): results are bit-equal across the paths.
+template <typename T>
+__device__ __forceinline__ uint32_t affine_relu_pair16(uint32_t w, float sc0, float sh0, float sc1, float sh1)
+{
+    const float lo = fmaxf(fmaf(h16<T>::lo(w), sc0, sh0), 0.0f);
+    const float hi = fmaxf(fmaf(h16<T>::hi(w), sc1, sh1), 0.0f);
+    return h16<T>::pack2(lo, hi);
+}
+template <typename T>
+__device__ __forceinline__ void affine_relu_chunk16(uint4 &v, const float *sc, const float *sh)
+{
+    uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w[e] = affine_relu_pair16<T>(w[e], sc[2 * e], sh[2 * e], sc[2 * e + 1], sh[2 * e + 1]);
+    v = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // ---- wave64 reductions over DPP (no LDS, no ds_bpermute) -----------------------------------
 // butterfly inside each row of 16 lanes, then row_bcast15 / row_bcast31 fold the four rows;
 // lane 63 ends with the full result, which v_readlane turns into a wave-uniform SGPR value.
@@ -277,3 +296,29 @@ extern "C" int ppt_get_wave_priority(void);
 // Share of the chip the PERSISTENT point-tower kernels (one long-lived workgroup per CU: the mini-PointNet kernels) size their
 // grids for, in percent; see ppt_set_persistent_occupancy in include/ppt_hip.h.
 extern "C" int ppt_get_persistent_occupancy(void);
+
+// Grid of a persistent kernel: `per_cu` workgroups per compute unit of the stream's device, scaled by that share (fewer when the
+// caller leaves room for the other stream), at least 8, never more than the units of work there are.
+static inline int ppt_persistent_grid(int64_t units, int per_cu, hipStream_t s)
+{
+    int64_t want = (int64_t)ppt_cu_count(s) * per_cu * ppt_get_persistent_occupancy() / 100;
+    want = want < 8 ? 8 : want;
+    return (int)(units < want ? units : want);
+}
+
+// Raise the dynamic-LDS limit of the listed kernels to `bytes`, once per process: PPT_RAISE_LDS_ONCE(bytes, kernel, kernel, ...).
+#define PPT_RAISE_LDS_ONCE(bytes, ...)                                                                                    \
+    do {                                                                                                                  \
+        static const int once__ = [] {                                                                                    \
+            for (const void *k__ : {__VA_ARGS__}) (void)hipFuncSetAttribute(k__, hipFuncAttributeMaxDynamicSharedMemorySize, (bytes)); \
+            return 0;                                                                                                     \
+        }();                                                                                                              \
+        (void)once__;                                                                                                     \
+    } while (0)
+
+// The two-format launch: fn(F{}) with F = f16_t or bf16_t for dtype = PPT_F16 / PPT_BF16 (checked by the caller):
+//     ppt_launch16(dtype, [&](auto f) { hipLaunchKernelGGL((kernel<decltype(f), ...>), ...); });
+template <typename Fn> static inline void ppt_launch16(int dtype, Fn &&fn)
+{
+    if (dtype == PPT_F16) fn(f16_t{}); else fn(bf16_t{});
+}

@@ -723,10 +723,22 @@ def test_col_sums_matches_torch(ops, M, D, pad):
     assert torch.equal(out, ops.col_sums(x))
 
 
-@pytest.mark.parametrize("groups", [1, 7, 4096])
-def test_mini_pointnet_conv12_is_the_prologue_gemm(ops, groups):
-    """ppt_mini_pointnet_conv12_bf16 against ppt_gemm(PPT_A_CONV1 + bias + pool over 32 rows): same expression, same
-    summation order -> bit-identical y2 and group maxima; and against fp64 within bf16 rounding."""
+def _both_formats(*groups):
+    """(T, groups) cases of the mini-PointNet kernel tests: every group count in bfloat16 (ids "1", "7", ...: the names these
+    cases had when the tests ran bfloat16 only) and in float16, the format production runs (ids "float16-1", ...)."""
+    return pytest.mark.parametrize("T,groups", [pytest.param(torch.bfloat16, n, id=str(n)) for n in groups]
+                                   + [pytest.param(torch.float16, n, id="float16-%d" % n) for n in groups])
+
+
+def _rel16(T, bf16_bound):
+    """a bound stated for bfloat16, scaled to T by the ratio of the formats' unit roundoff (2^-8 -> 2^-11 for float16)"""
+    return bf16_bound * (2.0 ** -3 if T == torch.float16 else 1.0)
+
+
+@_both_formats(1, 7, 4096)
+def test_mini_pointnet_conv12_is_the_prologue_gemm(ops, T, groups):
+    """ppt_mini_pointnet_conv12_half against ppt_gemm(PPT_A_CONV1 + bias + pool over 32 rows): same expression, same
+    summation order -> bit-identical y2 and group maxima in both 16-bit formats; and against fp64 within the format's rounding."""
     g = torch.Generator(device="cuda").manual_seed(groups)
     M = groups * 32
     pts = torch.randn(M, 3, device="cuda", generator=g) * 0.3
@@ -734,17 +746,17 @@ def test_mini_pointnet_conv12_is_the_prologue_gemm(ops, groups):
     b1 = torch.randn(128, device="cuda", generator=g) * 0.1
     sc = 1.0 + 0.1 * torch.randn(128, device="cuda", generator=g)
     sh = 0.1 * torch.randn(128, device="cuda", generator=g)
-    w2 = (torch.randn(256, 128, device="cuda", generator=g) / 128 ** 0.5).to(torch.bfloat16)
+    w2 = (torch.randn(256, 128, device="cuda", generator=g) / 128 ** 0.5).to(T)
     b2 = torch.randn(256, device="cuda", generator=g) * 0.1
     y2, gm = ops.mini_pointnet_conv12(pts, w1, b1, sc, sh, w2, b2)
-    gm_ref = torch.empty((groups, 256), dtype=torch.bfloat16, device="cuda")
-    y2_ref = ops.gemm(None, w2, out_dtype=torch.bfloat16, a_mode=ops.A_CONV1, pts=pts, w1=w1, b1=b1, a_scale=sc, a_shift=sh,
+    gm_ref = torch.empty((groups, 256), dtype=T, device="cuda")
+    y2_ref = ops.gemm(None, w2, out_dtype=T, a_mode=ops.A_CONV1, pts=pts, w1=w1, b1=b1, a_scale=sc, a_shift=sh,
                       bias=b2, pool_max=gm_ref)
     assert torch.equal(y2, y2_ref) and torch.equal(gm, gm_ref)
     a = torch.relu(sc.double() * (pts.double() @ w1.double().t() + b1.double()) + sh.double())
-    ref = a.to(torch.bfloat16).double() @ w2.double().t() + b2.double()
-    assert (y2.double() - ref).abs().max().item() < 2e-2 * max(1.0, ref.abs().max().item())
-    assert torch.equal(gm, y2.view(groups, 32, 256).float().amax(1).to(torch.bfloat16))
+    ref = a.to(T).double() @ w2.double().t() + b2.double()
+    assert (y2.double() - ref).abs().max().item() < _rel16(T, 2e-2) * max(1.0, ref.abs().max().item())
+    assert torch.equal(gm, y2.view(groups, 32, 256).float().amax(1).to(T))
 
 
 @pytest.mark.parametrize("B,Q,K,C", [(2, 100, 4, 512), (3, 257, 4, 384), (1, 33, 16, 64)])
@@ -869,37 +881,40 @@ def test_affine_conv_pool_is_the_prologue_gemm(ops, K, N, pr):
     assert (pmax.double() - v.view(M // pr, pr, N).amax(1)).abs().max().item() < 2e-4 * max(1.0, v.abs().max().item())
 
 
-@pytest.mark.parametrize("groups", [1, 5, 2048])
-def test_mini_pointnet_conv4_is_the_prologue_gemm(ops, groups):
-    """ppt_mini_pointnet_conv4_bf16 against ppt_gemm(PPT_A_AFFINE_RELU + bias + pool over 32 rows): bit-identical group maxima."""
+@_both_formats(1, 5, 300, 2048)
+def test_mini_pointnet_conv4_is_the_prologue_gemm(ops, T, groups):
+    """ppt_mini_pointnet_conv4_half against ppt_gemm(PPT_A_AFFINE_RELU + bias + pool over 32 rows): bit-identical group maxima in
+    both 16-bit formats.  300 groups: more groups than the grid of one persistent workgroup per CU has workgroups, fewer than twice as
+    many -- some workgroups take two groups, the others one (the clamped prefetch of csrc/group_lds.h on both sides)."""
     g = torch.Generator(device="cuda").manual_seed(groups)
     M = 32 * groups
-    A = torch.randn(M, 512, device="cuda", generator=g).to(torch.bfloat16)
+    A = torch.randn(M, 512, device="cuda", generator=g).to(T)
     sc = 1.0 + 0.2 * torch.randn(512, device="cuda", generator=g)
     sh = 0.2 * torch.randn(512, device="cuda", generator=g)
-    w = (torch.randn(256, 512, device="cuda", generator=g) / 512 ** 0.5).to(torch.bfloat16)
+    w = (torch.randn(256, 512, device="cuda", generator=g) / 512 ** 0.5).to(T)
     b = torch.randn(256, device="cuda", generator=g) * 0.1
     tok = ops.mini_pointnet_conv4(A, sc, sh, w, b)
-    ref = torch.empty((groups, 256), dtype=torch.bfloat16, device="cuda")
+    ref = torch.empty((groups, 256), dtype=T, device="cuda")
     ops.gemm(A, w, a_mode=ops.A_AFFINE_RELU, a_scale=sc, a_shift=sh, bias=b, pool_max=ref, want_out=False)
     assert torch.equal(tok, ref)
-    a = torch.relu(A.double() * sc.double() + sh.double()).to(torch.bfloat16).double()
+    a = torch.relu(A.double() * sc.double() + sh.double()).to(T).double()
     v = (a @ w.double().t() + b.double()).view(groups, 32, 256).amax(1)
-    assert (tok.double() - v).abs().max().item() < 2e-2 * max(1.0, v.abs().max().item())
+    assert (tok.double() - v).abs().max().item() < _rel16(T, 2e-2) * max(1.0, v.abs().max().item())
 
 
-@pytest.mark.parametrize("groups", [1, 5, 2048])
-def test_mini_pointnet_conv3_is_the_group_add_gemm(ops, groups):
-    """ppt_mini_pointnet_conv3_bf16 against ppt_gemm(group_add + column statistics): bit-identical y3, equal BatchNorm partials."""
+@_both_formats(1, 5, 300, 2048)
+def test_mini_pointnet_conv3_is_the_group_add_gemm(ops, T, groups):
+    """ppt_mini_pointnet_conv3_half against ppt_gemm(group_add + column statistics): bit-identical y3, equal BatchNorm partials, in
+    both 16-bit formats.  300 groups: some persistent workgroups take two groups, the others one (see the conv4 test)."""
     g = torch.Generator(device="cuda").manual_seed(groups + 3)
     M = 32 * groups
-    A = torch.randn(M, 256, device="cuda", generator=g).to(torch.bfloat16)
-    w = (torch.randn(512, 256, device="cuda", generator=g) / 16).to(torch.bfloat16)
+    A = torch.randn(M, 256, device="cuda", generator=g).to(T)
+    w = (torch.randn(512, 256, device="cuda", generator=g) / 16).to(T)
     gt = torch.randn(groups, 512, device="cuda", generator=g)
     st = (torch.empty((groups, 512), device="cuda"), torch.empty((groups, 512), device="cuda"))
     y = ops.mini_pointnet_conv3(A, w, gt, st)
     rst = (torch.empty((groups, 512), device="cuda"), torch.empty((groups, 512), device="cuda"))
-    ref = ops.gemm(A, w, out_dtype=torch.bfloat16, group_add=gt, group_rows=32, col_stats=rst)
+    ref = ops.gemm(A, w, out_dtype=T, group_add=gt, group_rows=32, col_stats=rst)
     assert torch.equal(y, ref)
     assert torch.equal(ops.mini_pointnet_conv3(A, w, gt), ref)                   # eval mode: no partials
     assert (st[0] - rst[0]).abs().max().item() < 1e-4 * max(1.0, rst[0].abs().max().item())
@@ -2122,12 +2137,13 @@ def test_mini_pointnet_conv34_matches_fp32_math_on_the_same_operands(ops, T, til
         assert (tok.float() - toku.float()).abs().max().item() < 0.05 * max(1.0, ref.abs().max().item())
 
 
-def test_mini_pointnet_conv3_statistics_pass_without_store(ops):
+@_both_formats(333)
+def test_mini_pointnet_conv3_statistics_pass_without_store(ops, T, groups):
     """ppt_mini_pointnet_conv3_half with y == NULL: the same BatchNorm partials, bit for bit, as the storing pass."""
     g = torch.Generator().manual_seed(3)
-    M = 32 * 333
-    y2 = torch.randn(M, 256, generator=g).cuda().to(torch.float16)
-    w = (torch.randn(512, 256, generator=g) * 0.06).cuda().to(torch.float16)
+    M = 32 * groups
+    y2 = torch.randn(M, 256, generator=g).cuda().to(T)
+    w = (torch.randn(512, 256, generator=g) * 0.06).cuda().to(T)
     gterm = torch.randn(M // 32, 512, generator=g).cuda()
     st_a = (torch.empty(M // 32, 512, device="cuda"), torch.empty(M // 32, 512, device="cuda"))
     st_b = (torch.empty(M // 32, 512, device="cuda"), torch.empty(M // 32, 512, device="cuda"))

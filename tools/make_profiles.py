@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # weight-stationary short-K linears and the fused ViT MLP (text_mlp_kernel<FORM, ..>: FORM 1 = PPT_BF16, 2 = PPT_F16; 0 is its split16 form).
 # The attention kernels are not part of it, neither form of attn_fwd_stream<FORM, ..>: they join the MFMA-utilisation table by their
 # attn_ name, each instantiation a row of its own.
-GEMM_BF16 = r"gemm_kernel.*<(unsigned short|f16_t)|gemm256_kernel|gemm_tn_kernel|mpn[134]_kernel|rowgemm_kernel|vit_mlp_kernel|vit_mlp3_kernel|text_mlp_kernel<[12],|lnlin_kernel"
+GEMM_BF16 = r"gemm_kernel.*<(unsigned short|f16_t)|gemm256_kernel|gemm_tn_kernel|mpn[134]_kernel|group_lds_kernel|rowgemm_kernel|vit_mlp_kernel|vit_mlp3_kernel|text_mlp_kernel<[12],|lnlin_kernel"
 CONFIGS = ("c2", "c3", "c4", "c5", "mlp")
 TRACE_STEPS = 40 + 5 + 10                   # burn-in + warm-up + timed steps of the traced command
 
@@ -76,7 +76,7 @@ def section(rnd, cfg, d, out):
         nf, nw = int(fam_f["count"].sum()), int(fam_w["count"].sum())
         if cfg == "c2" and nf:
             traffic = {
-                "kernel": "16-bit MFMA GEMM family (gemm_kernel* <unsigned short | f16_t>, gemm_tn_kernel, mpn1 / mpn3 / mpn4_kernel, rowgemm_kernel, lnlin_kernel, vit_mlp3_kernel, text_mlp_kernel)",
+                "kernel": "16-bit MFMA GEMM family (gemm_kernel* <unsigned short | f16_t>, gemm_tn_kernel, mpn1_kernel, group_lds_kernel (mpn3.hip / mpn4.hip), rowgemm_kernel, lnlin_kernel, vit_mlp3_kernel, text_mlp_kernel)",
                 "command": "PPT_HIP_GRAPHS=0 rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) --output-format csv -- "
                            "python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-roofline --no-parity-mode --no-secondary",
                 "launches_counted": nf, "fetch_size_kb_sum": float(fam_f["sum"].sum()), "write_size_kb_sum": float(fam_w["sum"].sum()),
