@@ -30,7 +30,7 @@
 // AttnForm<FORM> holds what differs; the row map, the peel, the masking, the online softmax and the tile pipeline are one text.
 #include <stdlib.h>
 #include <type_traits>
-#include "attn_common.h"
+#include "attn_bwd16.h"
 
 namespace {
 
@@ -286,10 +286,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_stream(const typename AttnFor
     const int nkt = CAUSAL ? min((T + KVT - 1) / KVT, q_hi / KVT + 1) : (Tk + KVT - 1) / KVT;
 
     f32x16_t ot[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) ot[i][e] = 0.f;
+    ATTN_ZERO2(ot[0], ot[1]);
     float m = -INFINITY, l = 0.f;
     if (peel) {
         const E *kl = kb + am_row(Tfull, P, b, T - 1) * rs, *vl = vb + am_row(Tfull, P, b, T - 1) * rs;
@@ -313,10 +310,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_stream(const typename AttnFor
         if (active) {
             const unsigned char *Kc = smem + cur * IMG, *Vc = smem + (2 + cur) * IMG;
             f32x16_t st[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) st[i][e] = 0.f;
+            ATTN_ZERO2(st[0], st[1]);
             A::qk(st, Kc, q, r, h);
             const bool need_mask = (kt * KVT + KVT > Tk) || (CAUSAL && kt * KVT + KVT - 1 > q0);
             if (need_mask) {
@@ -504,11 +498,7 @@ __global__ __launch_bounds__(512) void attn_fwd_resident(const bf16_t *__restric
         const unsigned char *Kc = Ks + kt * TILE, *Vc = Vs + kt * TILE;
         f32x16_t st[2][2];
 #pragma unroll
-        for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) st[qt][sub][e] = 0.f;
+        for (int qt = 0; qt < 2; ++qt) ATTN_ZERO2(st[qt][0], st[qt][1]);
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
             uint4 kf[2];
@@ -686,7 +676,7 @@ constexpr int DKV_SMEM = 2 * (4 * QTILE + 256);   // per stage: Q row image, Q t
 // INLINE_DELTA: delta[q] = sum_d out[q, d] * dout[q, d] is computed while the q tile is staged (the eight threads that stage a
 // row hold its eight 16-byte chunks) instead of being read from the array a separate kernel filled: one node less in the
 // prompt chain per layer.
-template <typename F, bool CAUSAL, bool INLINE_DELTA, bool WHOLE_PREFIX = false>
+template <typename F, bool CAUSAL, bool INLINE_DELTA>
 __device__ __forceinline__ void attn_bwd_dkv_body(const bf16_t *__restrict__ qkv, const bf16_t *__restrict__ out, const bf16_t *__restrict__ dout,
                                                   const float *__restrict__ lse, const float *__restrict__ delta,
                                                   bf16_t *__restrict__ dqkv, int Tfull, int H, float scale, int P, int C,
@@ -698,12 +688,6 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const bf16_t *__restrict__ qkv
     const int bh = by, b = bh / H, head = bh % H;
     const int64_t rs = 3 * (int64_t)H * HD, os = (int64_t)H * HD;
     const int T = am_len(Tfull, P, C, b), q_lo = am_qlo(P, C, b);
-    // WHOLE_PREFIX: the prefix sequence's workgroup (b == C) walks ALL physical rows as queries -- every prompt's own rows attend
-    // to every shared key, the shared rows causally among themselves (key <= row covers both: own rows sit at >= P) -- and
-    // writes dK / dV of the shared keys itself, in one fixed order; the prompts' workgroups then skip their shared keys.  No
-    // fp32 partials, no reduction kernel behind this one.
-    const bool pfx = WHOLE_PREFIX && P > 0 && b == C;
-    const int Tq = pfx ? P + C * (Tfull - P) : T;
     const bf16_t *qb = qkv + head * HD;
     const bf16_t *kb = qb + H * HD, *vb = qb + 2 * H * HD;
     const bf16_t *gb = dout + head * HD;
@@ -724,11 +708,9 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const bf16_t *__restrict__ qkv
     }
     f32x16_t dvt[2], dkt[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { dvt[i][e] = 0.f; dkt[i][e] = 0.f; }
+    for (int i = 0; i < 2; ++i) ATTN_ZERO2(dvt[i], dkt[i]);
 
-    const int nqt = (Tq + QT - 1) / QT;
+    const int nqt = (T + QT - 1) / QT;
     // queries before the block's first key see none of it; queries below q_lo belong to the prefix sequence, not to this one
     const int qt0 = max(CAUSAL ? (int)(bx * 128) / QT : 0, q_lo / QT);
     uint4 sq, sg, so = make_uint4(0, 0, 0, 0);
@@ -737,8 +719,8 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const bf16_t *__restrict__ qkv
     auto load_tile = [&](int qt) {
         const int q = qt * QT + srow;
         sq = sg = so = make_uint4(0, 0, 0, 0);
-        if (q < Tq) {
-            const int64_t qr = pfx ? (int64_t)q : am_row(Tfull, P, b, q);
+        if (q < T) {
+            const int64_t qr = am_row(Tfull, P, b, q);
             sq = *reinterpret_cast<const uint4 *>(qb + qr * rs + sch * 8);
             sg = *reinterpret_cast<const uint4 *>(gb + qr * os + sch * 8);
             if constexpr (INLINE_DELTA) so = *reinterpret_cast<const uint4 *>(out + head * HD + qr * os + sch * 8);
@@ -747,12 +729,12 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const bf16_t *__restrict__ qkv
             // the row's eight chunks sit in eight consecutive lanes: three xor steps leave the row sum in all of them
             float d = dot8_bf16<F>(sg, so);
             d += __shfl_xor(d, 1); d += __shfl_xor(d, 2); d += __shfl_xor(d, 4);
-            const bool own = q < Tq && q >= q_lo;
+            const bool own = q < T && q >= q_lo;
             sdr = own ? d : 0.f;
             if (threadIdx.x < QT) {
                 const int q2 = qt * QT + threadIdx.x;
-                const bool own2 = q2 < Tq && q2 >= q_lo;
-                sl = own2 ? lse[pfx ? (int64_t)q2 * H + head : am_stat(Tfull, P, H, b, head, q2)] * 1.4426950408889634f : INFINITY;
+                const bool own2 = q2 < T && q2 >= q_lo;
+                sl = own2 ? lse[am_stat(Tfull, P, H, b, head, q2)] * 1.4426950408889634f : INFINITY;
             }
         } else if (threadIdx.x < QT) {
             const int q2 = qt * QT + threadIdx.x;
@@ -774,9 +756,8 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const bf16_t *__restrict__ qkv
             reinterpret_cast<float *>(base + 4 * QTILE + 128)[threadIdx.x] = sd;
         }
     };
-    const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
-    const int tr_row = 4 * (g >> 1) + tq;
-    const int tr_dbyte = (16 * (g & 1) + 4 * tp) * 2;
+    int tr_row, tr_dbyte;
+    tr_lane(lane, tr_row, tr_dbyte);
 
     if (qt0 < nqt) {
         load_tile(qt0);
@@ -791,73 +772,18 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const bf16_t *__restrict__ qkv
             const unsigned char *base = smem + cur * (4 * QTILE + 256);
             const float *L2 = reinterpret_cast<const float *>(base + 4 * QTILE);
             const float *DL = reinterpret_cast<const float *>(base + 4 * QTILE + 128);
-            f32x16_t sa, dp;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { sa[e] = 0.f; dp[e] = 0.f; }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const uint4 qa = (*reinterpret_cast<const uint4 *>(base + 0 * QTILE + k_off(r, 2 * kk + h)));
-                const uint4 ga = (*reinterpret_cast<const uint4 *>(base + 2 * QTILE + k_off(r, 2 * kk + h)));
-                sa = h16<F>::mfma32(qa, kf[kk], sa);
-                dp = h16<F>::mfma32(ga, vf[kk], dp);
-            }
-            const bool diag = CAUSAL && qt * QT < k0 + 32;        // some (q, key) pairs of this tile are masked
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const float4 l4 = *reinterpret_cast<const float4 *>(L2 + 8 * gq + 4 * h);
-                const float4 d4 = *reinterpret_cast<const float4 *>(DL + 8 * gq + 4 * h);
-                const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dv[4] = {d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int e = 4 * gq + j;
-                    float pv = __builtin_amdgcn_exp2f(fmaf(sa[e], c, -lv[j]));
-                    if (diag && key > qt * QT + 8 * gq + 4 * h + j) pv = 0.f;
-                    sa[e] = pv;
-                    dp[e] = pv * (dp[e] - dv[j]) * scale;
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const uint4 pf = pack8<F>(sa, s), df = pack8<F>(dp, s);
-#pragma unroll
-                for (int dtile = 0; dtile < 2; ++dtile) {
-                    const uint4 gt = tr_frag(base + 3 * QTILE, 16 * s + tr_row, tr_dbyte + 64 * dtile);   // dO^T
-                    dvt[dtile] = h16<F>::mfma32(gt, pf, dvt[dtile]);
-                    const uint4 qt_ = tr_frag(base + 1 * QTILE, 16 * s + tr_row, tr_dbyte + 64 * dtile);  // Q^T
-                    dkt[dtile] = h16<F>::mfma32(qt_, df, dkt[dtile]);
-                }
-            }
+            ATTN_BWD_DKV_STEP(base + 0 * QTILE, base + 1 * QTILE, base + 2 * QTILE, base + 3 * QTILE, L2, DL, 0, qt * QT);
         }
         if (qt + 1 < nqt) write_tile(cur ^ 1);
         __syncthreads();
     }
-    if (WHOLE_PREFIX && P > 0 && key < P && !pfx) {
-        // (a shared key seen from a prompt: the prefix workgroup owns it)
-    } else if (!WHOLE_PREFIX && key < T && P > 0 && key < P) {
-        // a SHARED key: this virtual sequence's contribution goes to its fp32 partial slot [b][key][K | V][H * HD]; the
-        // slots are folded in a fixed order by attn_prefix_reduce (no atomics)
-        float *pk = part + (((int64_t)b * P + key) * 2) * os + head * HD, *pv = pk + os;
-#pragma unroll
-        for (int dtile = 0; dtile < 2; ++dtile)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int d = 32 * dtile + 8 * gq + 4 * h;
-                *reinterpret_cast<float4 *>(pk + d) = make_float4(dkt[dtile][4 * gq], dkt[dtile][4 * gq + 1], dkt[dtile][4 * gq + 2], dkt[dtile][4 * gq + 3]);
-                *reinterpret_cast<float4 *>(pv + d) = make_float4(dvt[dtile][4 * gq], dvt[dtile][4 * gq + 1], dvt[dtile][4 * gq + 2], dvt[dtile][4 * gq + 3]);
-            }
+    if (key < T && P > 0 && key < P) {
+        // a SHARED key: this virtual sequence's contribution goes to its fp32 partial slot
+        float *pk = part + (((int64_t)b * P + key) * 2) * os + head * HD;
+        attn_store_dkdv_part(pk, pk + os, dkt, dvt, h);
     } else if (key < T) {
         bf16_t *ok = dqkv + am_row(Tfull, P, b, key) * rs + head * HD + H * HD;
-        bf16_t *ov = ok + H * HD;
-#pragma unroll
-        for (int dtile = 0; dtile < 2; ++dtile)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int d = 32 * dtile + 8 * gq + 4 * h;
-                *reinterpret_cast<uint2 *>(ok + d) = make_uint2(h16<F>::pack2(dkt[dtile][4 * gq], dkt[dtile][4 * gq + 1]),
-                                                                 h16<F>::pack2(dkt[dtile][4 * gq + 2], dkt[dtile][4 * gq + 3]));
-                *reinterpret_cast<uint2 *>(ov + d) = make_uint2(h16<F>::pack2(dvt[dtile][4 * gq], dvt[dtile][4 * gq + 1]),
-                                                                 h16<F>::pack2(dvt[dtile][4 * gq + 2], dvt[dtile][4 * gq + 3]));
-            }
+        attn_store_dkdv16<F>(ok, ok + H * HD, dkt, dvt, h);
     }
 }
 
@@ -942,13 +868,9 @@ __device__ __forceinline__ void attn_bwd_dq_body(const bf16_t *__restrict__ qkv,
     const int q_hi = min(T, (int)(bx + 1) * QB) - 1;
     const int nkt = CAUSAL ? min((T + KVT - 1) / KVT, q_hi / KVT + 1) : (T + KVT - 1) / KVT;
     f32x16_t dqt[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) dqt[i][e] = 0.f;
-    const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
-    const int tr_row = 4 * (g >> 1) + tq;
-    const int tr_dbyte = (16 * (g & 1) + 4 * tp) * 2;
+    ATTN_ZERO2(dqt[0], dqt[1]);
+    int tr_row, tr_dbyte;
+    tr_lane(lane, tr_row, tr_dbyte);
 
     load_tile(0);
     write_tile(0);
@@ -961,50 +883,13 @@ __device__ __forceinline__ void attn_bwd_dq_body(const bf16_t *__restrict__ qkv,
             const unsigned char *base = smem + cur * 3 * TILE;
             const bool need_mask = (kt * KVT + KVT > T) || (CAUSAL && kt * KVT + KVT - 1 > q0);
 #pragma unroll
-            for (int sub = 0; sub < 2; ++sub) {
-                f32x16_t sa, dp;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) { sa[e] = 0.f; dp[e] = 0.f; }
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    const uint4 ka = (*reinterpret_cast<const uint4 *>(base + 0 * TILE + k_off(32 * sub + r, 2 * kk + h)));
-                    const uint4 va = (*reinterpret_cast<const uint4 *>(base + 2 * TILE + k_off(32 * sub + r, 2 * kk + h)));
-                    sa = h16<F>::mfma32(ka, qf[kk], sa);     // S^T  [key][q]
-                    dp = h16<F>::mfma32(va, gf[kk], dp);     // dP^T [key][q]
-                }
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    float pv = __builtin_amdgcn_exp2f(fmaf(sa[e], c, -l2));
-                    if (need_mask) {
-                        const int kx = kt * KVT + 32 * sub + (e & 3) + 8 * (e >> 2) + 4 * h;
-                        if (kx >= T || (CAUSAL && kx > qrow)) pv = 0.f;
-                    }
-                    dp[e] = pv * (dp[e] - dl) * scale;
-                }
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const uint4 df = pack8<F>(dp, s);
-#pragma unroll
-                    for (int dtile = 0; dtile < 2; ++dtile) {
-                        const uint4 kt_ = tr_frag(base + 1 * TILE, 32 * sub + 16 * s + tr_row, tr_dbyte + 64 * dtile);   // K^T
-                        dqt[dtile] = h16<F>::mfma32(kt_, df, dqt[dtile]);
-                    }
-                }
-            }
+            for (int sub = 0; sub < 2; ++sub)
+                ATTN_BWD_DQ_STEP(base + 0 * TILE, base + 1 * TILE, base + 2 * TILE, 32 * sub, kt * KVT + 32 * sub, need_mask);
         }
         if (kt + 1 < nkt) write_tile(cur ^ 1);
         __syncthreads();
     }
-    if (own) {
-        bf16_t *oq = dqkv + am_row(Tfull, P, b, qrow) * rs + head * HD;
-#pragma unroll
-        for (int dtile = 0; dtile < 2; ++dtile)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq)
-                *reinterpret_cast<uint2 *>(oq + 32 * dtile + 8 * gq + 4 * h) =
-                    make_uint2(h16<F>::pack2(dqt[dtile][4 * gq], dqt[dtile][4 * gq + 1]),
-                               h16<F>::pack2(dqt[dtile][4 * gq + 2], dqt[dtile][4 * gq + 3]));
-    }
+    if (own) attn_store_dq16<F>(dqkv + am_row(Tfull, P, b, qrow) * rs + head * HD, dqt, h);
 }
 
 template <bool CAUSAL, typename F>
@@ -1018,10 +903,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_mfma(const bf16_t *__restr
 
 // One launch for the whole backward of a SHORT sequence (T <= 128: one key block and one query block per (sequence, head);
 // the CLIP text tower, 37 positions): blockIdx.x == 0 computes dK / dV, blockIdx.x == 1 computes dQ, both form delta
-// themselves -- attn_delta + dkv + dq (three nodes of the prompt chain per layer) become one.  (WHOLE_PREFIX, which would also
-// absorb attn_prefix_reduce, is compiled out: the prefix workgroup's walk over all 817 rows is 26 dependent tile iterations
-// of ~1.1 us each -- the next tile's loads are only one iteration ahead -- and made the launch ~29 us instead of ~3 + a 4.5 us
-// reduction: prompt chain alone 1.97 -> 2.33 ms.)
+// themselves -- attn_delta + dkv + dq (three nodes of the prompt chain per layer) become one.
 #ifndef PPT_SHORT_OCC
 #define PPT_SHORT_OCC 2
 #endif
@@ -1036,12 +918,12 @@ __global__ __launch_bounds__(256, PPT_SHORT_OCC) void attn_bwd_short_mfma(const 
     // gridDim.x == 2: one workgroup per role; == 1: ONE workgroup runs both roles back to back (half the workgroups: with two
     // 208-VGPR workgroups per CU, 656 role workgroups of the 41 x 8 (sequence, head) pairs were two rounds on 512 slots)
 #ifdef PPT_SHORT_ROLE   // (diagnostic build: one role only)
-    if (PPT_SHORT_ROLE == 0) { attn_bwd_dkv_body<F, CAUSAL, true, false>(qkv, out, dout, lse, nullptr, dqkv, Tfull, H, scale, P, C, part, smem, 0, blockIdx.y); return; }
+    if (PPT_SHORT_ROLE == 0) { attn_bwd_dkv_body<F, CAUSAL, true>(qkv, out, dout, lse, nullptr, dqkv, Tfull, H, scale, P, C, part, smem, 0, blockIdx.y); return; }
     if (PPT_SHORT_ROLE == 1) { attn_bwd_dq_body<F, CAUSAL, true>(qkv, out, dout, lse, nullptr, dqkv, Tfull, H, scale, P, C, smem, 0, blockIdx.y); return; }
     if (PPT_SHORT_ROLE == 2) return;
 #endif
     if (gridDim.x == 1 || blockIdx.x == 0)
-        attn_bwd_dkv_body<F, CAUSAL, true, false>(qkv, out, dout, lse, nullptr, dqkv, Tfull, H, scale, P, C, part, smem, 0, blockIdx.y);
+        attn_bwd_dkv_body<F, CAUSAL, true>(qkv, out, dout, lse, nullptr, dqkv, Tfull, H, scale, P, C, part, smem, 0, blockIdx.y);
     if (gridDim.x == 1) __syncthreads();
     if (gridDim.x == 1 || blockIdx.x == 1)
         attn_bwd_dq_body<F, CAUSAL, true>(qkv, out, dout, lse, nullptr, dqkv, Tfull, H, scale, P, C, smem, 0, blockIdx.y);
@@ -1114,9 +996,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_tiny_mfma(const bf16_t *__res
         }
     }
     __syncthreads();
-    const int g4 = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
-    const int tr_row = 4 * (g4 >> 1) + tq;
-    const int tr_dbyte = (16 * (g4 & 1) + 4 * tp) * 2;
+    int tr_row, tr_dbyte;
+    tr_lane(lane, tr_row, tr_dbyte);
 
     if (w < 2) {
         // ---- dK / dV of keys 32 w .. 32 w + 31 (attn_bwd_dkv_body with K, V, Q, dO out of LDS)
@@ -1130,73 +1011,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_tiny_mfma(const bf16_t *__res
         }
         f32x16_t dvt[2], dkt[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { dvt[i][e] = 0.f; dkt[i][e] = 0.f; }
+    for (int i = 0; i < 2; ++i) ATTN_ZERO2(dvt[i], dkt[i]);
         const int nqt = (T + QT - 1) / QT;
         for (int qt = q_lo / QT; qt < nqt; ++qt) {
             if (CAUSAL && qt * QT + QT - 1 < k0) continue;
-            f32x16_t sa, dp;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { sa[e] = 0.f; dp[e] = 0.f; }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const uint4 qa = *reinterpret_cast<const uint4 *>(Qr + k_off(QT * qt + r, 2 * kk + h));
-                const uint4 ga = *reinterpret_cast<const uint4 *>(Gr + k_off(QT * qt + r, 2 * kk + h));
-                sa = h16<F>::mfma32(qa, kf[kk], sa);
-                dp = h16<F>::mfma32(ga, vf[kk], dp);
-            }
-            const bool diag = CAUSAL && qt * QT < k0 + 32;
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const float4 l4 = *reinterpret_cast<const float4 *>(L2 + QT * qt + 8 * gq + 4 * h);
-                const float4 d4 = *reinterpret_cast<const float4 *>(DL + QT * qt + 8 * gq + 4 * h);
-                const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dv[4] = {d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int e = 4 * gq + j;
-                    float pv = __builtin_amdgcn_exp2f(fmaf(sa[e], c, -lv[j]));
-                    if (diag && key > qt * QT + 8 * gq + 4 * h + j) pv = 0.f;
-                    sa[e] = pv;
-                    dp[e] = pv * (dp[e] - dv[j]) * scale;
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const uint4 pf = pack8<F>(sa, s), df = pack8<F>(dp, s);
-#pragma unroll
-                for (int dtile = 0; dtile < 2; ++dtile) {
-                    const uint4 gt = tr_frag(Gt, QT * qt + 16 * s + tr_row, tr_dbyte + 64 * dtile);   // dO^T
-                    dvt[dtile] = h16<F>::mfma32(gt, pf, dvt[dtile]);
-                    const uint4 qt_ = tr_frag(Qt, QT * qt + 16 * s + tr_row, tr_dbyte + 64 * dtile);  // Q^T
-                    dkt[dtile] = h16<F>::mfma32(qt_, df, dkt[dtile]);
-                }
-            }
+            ATTN_BWD_DKV_STEP(Qr, Qt, Gr, Gt, L2, DL, QT * qt, qt * QT);
         }
         if (key < T && P > 0 && key < P) {
-            // a SHARED key: the fp32 partial slot of this virtual sequence (folded in a fixed order by attn_prefix_reduce)
-            float *pk = part + (((int64_t)b * P + key) * 2) * os + head * HD, *pv = pk + os;
-#pragma unroll
-            for (int dtile = 0; dtile < 2; ++dtile)
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const int d = 32 * dtile + 8 * gq + 4 * h;
-                    *reinterpret_cast<float4 *>(pk + d) = make_float4(dkt[dtile][4 * gq], dkt[dtile][4 * gq + 1], dkt[dtile][4 * gq + 2], dkt[dtile][4 * gq + 3]);
-                    *reinterpret_cast<float4 *>(pv + d) = make_float4(dvt[dtile][4 * gq], dvt[dtile][4 * gq + 1], dvt[dtile][4 * gq + 2], dvt[dtile][4 * gq + 3]);
-                }
+            // a SHARED key: the fp32 partial slot of this virtual sequence
+            float *pk = part + (((int64_t)b * P + key) * 2) * os + head * HD;
+            attn_store_dkdv_part(pk, pk + os, dkt, dvt, h);
         } else if (key < T) {
             bf16_t *ok = dqkv + am_row(Tfull, P, b, key) * rs + head * HD + H * HD;
-            bf16_t *ov = ok + H * HD;
-#pragma unroll
-            for (int dtile = 0; dtile < 2; ++dtile)
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const int d = 32 * dtile + 8 * gq + 4 * h;
-                    *reinterpret_cast<uint2 *>(ok + d) = make_uint2(h16<F>::pack2(dkt[dtile][4 * gq], dkt[dtile][4 * gq + 1]),
-                                                                     h16<F>::pack2(dkt[dtile][4 * gq + 2], dkt[dtile][4 * gq + 3]));
-                    *reinterpret_cast<uint2 *>(ov + d) = make_uint2(h16<F>::pack2(dvt[dtile][4 * gq], dvt[dtile][4 * gq + 1]),
-                                                                     h16<F>::pack2(dvt[dtile][4 * gq + 2], dvt[dtile][4 * gq + 3]));
-                }
+            attn_store_dkdv16<F>(ok, ok + H * HD, dkt, dvt, h);
         }
     } else {
         // ---- dQ of queries 32 (w - 2) .. + 31 (attn_bwd_dq_body with Q, dO, K, V out of LDS; one 64-key tile)
@@ -1211,50 +1038,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_tiny_mfma(const bf16_t *__res
         const bool own = qrow < T && qrow >= q_lo;
         const float l2 = L2[qrow], dl = DL[qrow];
         f32x16_t dqt[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) dqt[i][e] = 0.f;
+    ATTN_ZERO2(dqt[0], dqt[1]);
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             if (32 * sub >= T || (CAUSAL && 32 * sub > q0 + 31)) continue;      // (no unmasked key in this half: it would add zeros)
-            f32x16_t sa, dp;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { sa[e] = 0.f; dp[e] = 0.f; }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const uint4 ka = *reinterpret_cast<const uint4 *>(Kr + k_off(32 * sub + r, 2 * kk + h));
-                const uint4 va = *reinterpret_cast<const uint4 *>(Vr + k_off(32 * sub + r, 2 * kk + h));
-                sa = h16<F>::mfma32(ka, qf[kk], sa);     // S^T  [key][q]
-                dp = h16<F>::mfma32(va, gf[kk], dp);     // dP^T [key][q]
-            }
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                float pv = __builtin_amdgcn_exp2f(fmaf(sa[e], c, -l2));
-                const int kx = 32 * sub + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (kx >= T || (CAUSAL && kx > qrow)) pv = 0.f;
-                dp[e] = pv * (dp[e] - dl) * scale;
-            }
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const uint4 df = pack8<F>(dp, s);
-#pragma unroll
-                for (int dtile = 0; dtile < 2; ++dtile) {
-                    const uint4 kt_ = tr_frag(Kt, 32 * sub + 16 * s + tr_row, tr_dbyte + 64 * dtile);   // K^T
-                    dqt[dtile] = h16<F>::mfma32(kt_, df, dqt[dtile]);
-                }
-            }
+            ATTN_BWD_DQ_STEP(Kr, Kt, Vr, 32 * sub, 32 * sub, true);
         }
-        if (own) {
-            bf16_t *oq = dqkv + am_row(Tfull, P, b, qrow) * rs + head * HD;
-#pragma unroll
-            for (int dtile = 0; dtile < 2; ++dtile)
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq)
-                    *reinterpret_cast<uint2 *>(oq + 32 * dtile + 8 * gq + 4 * h) =
-                        make_uint2(h16<F>::pack2(dqt[dtile][4 * gq], dqt[dtile][4 * gq + 1]),
-                                   h16<F>::pack2(dqt[dtile][4 * gq + 2], dqt[dtile][4 * gq + 3]));
-        }
+        if (own) attn_store_dq16<F>(dqkv + am_row(Tfull, P, b, qrow) * rs + head * HD, dqt, h);
     }
 }
 
@@ -1294,19 +1084,15 @@ extern "C" int ppt_attention_fwd_mfma_bf16(const void *qkv, void *out, float *ls
     // the ViT shape with enough (batch, head) pairs to fill the chip: K / V resident in LDS (attn_fwd_resident)
     static const bool resident_ok = getenv("PPT_ATTN_RESIDENT") == nullptr || atoi(getenv("PPT_ATTN_RESIDENT")) != 0;
     if (resident_ok && !causal && P == 0 && (T % KVT) == 1 && T - 1 >= 6 * KVT && T - 1 <= RES_MAXK && Bt * H >= 128) {
-#define PPT_RES_ATTR(FF, NN) (void)hipFuncSetAttribute((const void *)attn_fwd_resident<FF, NN>, hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS)
-        static const bool attr = [] {
-            PPT_RES_ATTR(bf16_t, 6); PPT_RES_ATTR(bf16_t, 7); PPT_RES_ATTR(bf16_t, 8);
-            PPT_RES_ATTR(f16_t, 6); PPT_RES_ATTR(f16_t, 7); PPT_RES_ATTR(f16_t, 8);
-            return true;
-        }();
-        (void)attr;
-#undef PPT_RES_ATTR
-#define PPT_RES_LAUNCH(FF, NN) hipLaunchKernelGGL((attn_fwd_resident<FF, NN>), dim3(Bt * H), dim3(512), RES_LDS, s, (const bf16_t *)qkv, (bf16_t *)out, lse, T, H, c, prio)
+        PPT_RAISE_LDS_ONCE(RES_LDS, (const void *)attn_fwd_resident<bf16_t, 6>, (const void *)attn_fwd_resident<bf16_t, 7>,
+                           (const void *)attn_fwd_resident<bf16_t, 8>, (const void *)attn_fwd_resident<f16_t, 6>,
+                           (const void *)attn_fwd_resident<f16_t, 7>, (const void *)attn_fwd_resident<f16_t, 8>);
         const int n = (T - 1) / KVT;
-        if (fmt == PPT_F16) { if (n == 6) PPT_RES_LAUNCH(f16_t, 6); else if (n == 7) PPT_RES_LAUNCH(f16_t, 7); else PPT_RES_LAUNCH(f16_t, 8); }
-        else { if (n == 6) PPT_RES_LAUNCH(bf16_t, 6); else if (n == 7) PPT_RES_LAUNCH(bf16_t, 7); else PPT_RES_LAUNCH(bf16_t, 8); }
-#undef PPT_RES_LAUNCH
+        ppt_launch16(fmt, [&](auto f) {
+            using F = decltype(f);
+            const auto k = n == 6 ? attn_fwd_resident<F, 6> : n == 7 ? attn_fwd_resident<F, 7> : attn_fwd_resident<F, 8>;
+            hipLaunchKernelGGL(k, dim3(Bt * H), dim3(512), RES_LDS, s, (const bf16_t *)qkv, (bf16_t *)out, lse, T, H, c, prio);
+        });
         PPT_CHECK_LAUNCH();
         return PPT_OK;
     }
@@ -1326,19 +1112,23 @@ extern "C" int ppt_attention_bwd_short_mfma_bf16(const void *qkv, const void *ou
     const int pairs = (Bt + (P > 0)) * H;
     if (tiny && T <= 64 && !((uintptr_t)dout & 15)) {
         const int prio = ppt_get_wave_priority();
-#define PPT_LAUNCH_TINY(CA, TT) hipLaunchKernelGGL((attn_bwd_tiny_mfma<CA, TT>), dim3(1, pairs), dim3(256), 0, s, (const bf16_t *)qkv, (const bf16_t *)out, (const bf16_t *)dout, lse, (bf16_t *)dqkv, T, H, scale, P, Bt, part, prio)
-        if (fmt == PPT_F16) { if (causal) PPT_LAUNCH_TINY(true, f16_t); else PPT_LAUNCH_TINY(false, f16_t); }
-        else { if (causal) PPT_LAUNCH_TINY(true, bf16_t); else PPT_LAUNCH_TINY(false, bf16_t); }
-#undef PPT_LAUNCH_TINY
+        ppt_launch16(fmt, [&](auto f) {
+            using F = decltype(f);
+            const auto k = causal ? attn_bwd_tiny_mfma<true, F> : attn_bwd_tiny_mfma<false, F>;
+            hipLaunchKernelGGL(k, dim3(1, pairs), dim3(256), 0, s, (const bf16_t *)qkv, (const bf16_t *)out, (const bf16_t *)dout, lse,
+                               (bf16_t *)dqkv, T, H, scale, P, Bt, part, prio);
+        });
         PPT_CHECK_LAUNCH();
         return PPT_OK;
     }
     dim3 grid(both && 2 * pairs > 512 ? 1 : 2, pairs);    // (two roles per workgroup once the role workgroups would not fit in one round)
     const int prio = ppt_get_wave_priority();
-#define PPT_LAUNCH_SHORT(CA, TT) hipLaunchKernelGGL((attn_bwd_short_mfma<CA, TT>), grid, dim3(256), 0, s, (const bf16_t *)qkv, (const bf16_t *)out, (const bf16_t *)dout, lse, (bf16_t *)dqkv, T, H, scale, P, Bt, part, prio)
-    if (fmt == PPT_F16) { if (causal) PPT_LAUNCH_SHORT(true, f16_t); else PPT_LAUNCH_SHORT(false, f16_t); }
-    else { if (causal) PPT_LAUNCH_SHORT(true, bf16_t); else PPT_LAUNCH_SHORT(false, bf16_t); }
-#undef PPT_LAUNCH_SHORT
+    ppt_launch16(fmt, [&](auto f) {
+        using F = decltype(f);
+        const auto k = causal ? attn_bwd_short_mfma<true, F> : attn_bwd_short_mfma<false, F>;
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const bf16_t *)qkv, (const bf16_t *)out, (const bf16_t *)dout, lse, (bf16_t *)dqkv, T, H,
+                           scale, P, Bt, part, prio);
+    });
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }
@@ -1349,12 +1139,13 @@ extern "C" int ppt_attention_bwd_mfma_bf16(const void *qkv, const void *dout, co
 {
     if (((uintptr_t)qkv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)dqkv & 7) || ((uintptr_t)part & 15)) return PPT_EUNSUPPORTED;
     dim3 grid((T + 127) / 128, (Bt + (P > 0)) * H);
-#define PPT_LAUNCH_BWD(CA, TT) do { \
-        hipLaunchKernelGGL((attn_bwd_dkv_mfma<CA, TT>), grid, dim3(256), 0, s, (const bf16_t *)qkv, (const bf16_t *)dout, lse, delta, (bf16_t *)dqkv, T, H, scale, P, Bt, part); \
-        hipLaunchKernelGGL((attn_bwd_dq_mfma<CA, TT>), grid, dim3(256), 0, s, (const bf16_t *)qkv, (const bf16_t *)dout, lse, delta, (bf16_t *)dqkv, T, H, scale, P, Bt); } while (0)
-    if (fmt == PPT_F16) { if (causal) PPT_LAUNCH_BWD(true, f16_t); else PPT_LAUNCH_BWD(false, f16_t); }
-    else { if (causal) PPT_LAUNCH_BWD(true, bf16_t); else PPT_LAUNCH_BWD(false, bf16_t); }
-#undef PPT_LAUNCH_BWD
+    ppt_launch16(fmt, [&](auto f) {
+        using F = decltype(f);
+        const auto dkv = causal ? attn_bwd_dkv_mfma<true, F> : attn_bwd_dkv_mfma<false, F>;
+        const auto dq = causal ? attn_bwd_dq_mfma<true, F> : attn_bwd_dq_mfma<false, F>;
+        hipLaunchKernelGGL(dkv, grid, dim3(256), 0, s, (const bf16_t *)qkv, (const bf16_t *)dout, lse, delta, (bf16_t *)dqkv, T, H, scale, P, Bt, part);
+        hipLaunchKernelGGL(dq, grid, dim3(256), 0, s, (const bf16_t *)qkv, (const bf16_t *)dout, lse, delta, (bf16_t *)dqkv, T, H, scale, P, Bt);
+    });
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }

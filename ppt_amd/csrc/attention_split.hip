@@ -105,9 +105,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_split16(const float *__re
     }
     f32x16_t dvt[2], dkt[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { dvt[i][e] = 0.f; dkt[i][e] = 0.f; }
+    for (int i = 0; i < 2; ++i) ATTN_ZERO2(dvt[i], dkt[i]);
 
     float run_v = 1.0f, run_k = 1.0f;                                  // the scales dvt / dkt currently carry
     const int nqt = (T + QT - 1) / QT;
@@ -171,8 +169,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_split16(const float *__re
         const bool active = k0 < T && (!CAUSAL || qt * QT + QT - 1 >= k0);       // wave-uniform
         if (active) {
             f32x16_t sa, dp;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { sa[e] = 0.f; dp[e] = 0.f; }
+            ATTN_ZERO2(sa, dp);
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 const int o = k_off(r, 2 * kk + h);
@@ -326,10 +323,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split16(const float *__res
     const int q_hi = min(T, (int)(blockIdx.x + 1) * QB) - 1;
     const int nkt = CAUSAL ? min((T + KVT - 1) / KVT, q_hi / KVT + 1) : (T + KVT - 1) / KVT;
     f32x16_t dqt[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) dqt[i][e] = 0.f;
+    ATTN_ZERO2(dqt[0], dqt[1]);
     float run_q = 1.0f;                                               // the scale dqt currently carries
     const float gsi = 1.0f / gs;
     const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
@@ -347,8 +341,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_split16(const float *__res
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub) {
                 f32x16_t sa, dp;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) { sa[e] = 0.f; dp[e] = 0.f; }
+                ATTN_ZERO2(sa, dp);
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
                     const int o = k_off(32 * sub + r, 2 * kk + h);

@@ -1,6 +1,6 @@
 // attn_common.h -- what the attention translation units (attention.hip, attention_mfma.hip, attention_split.hip) share besides the
-// row addressing of attn_rowmap.h: tile constants, the two swizzled LDS images, the XCD block map, the hi + lo half split of the
-// split16 form, and the launchers that cross from one file to another.  Internal: nothing here is part of include/ppt_hip.h.
+// row addressing of attn_rowmap.h: tile constants, the two swizzled LDS images, the transposed read and its lane geometry, accumulator
+// zeroing, the XCD block map, the hi + lo half split of the split16 form, and the launchers that cross from one file to another.  Internal: nothing here is part of include/ppt_hip.h.
 #pragma once
 #include "ppt_common.h"
 #include "attn_rowmap.h"
@@ -23,6 +23,22 @@ __device__ __forceinline__ uint4 tr_frag(const unsigned char *img, int row0, int
     f.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4_t *)(img + v_off(row0 + 8, dbyte)));
     return __builtin_bit_cast(uint4, f);
 }
+// per-lane constant part of tr_frag's arguments: lane = 16 g + 4 q + p supplies row q, columns 4 p .. 4 p + 3.  Used by the 16-bit
+// backward kernels; the forward kernels and attention_split.hip keep these three lines written out, because with the call their
+// register allocation changed (tools/kernel_isa_diff.py, profiles/r14_attention_bwd.md).
+__device__ __forceinline__ void tr_lane(int lane, int &tr_row, int &tr_dbyte)
+{
+    const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
+    tr_row = 4 * (g >> 1) + tq;                 // + the 16-row step's first row
+    tr_dbyte = (16 * (g & 1) + 4 * tp) * 2;     // + 64 * dtile
+}
+
+// Two accumulators to zero, element by element (four: a loop over the pairs).  A macro: as a function (accumulators or arrays
+// of them by reference) and as `= {}` at the declaration it moved the scalar set-up code of the backward kernels.
+#define ATTN_ZERO2(a, b)                                                                            \
+    do {                                                                                            \
+        _Pragma("unroll") for (int e_ = 0; e_ < 16; ++e_) { (a)[e_] = 0.f; (b)[e_] = 0.f; }         \
+    } while (0)
 
 // Workgroup -> (query block, batch x head): the dispatcher deals consecutive workgroups round-robin to the 8 XCDs, each with an
 // L2 of its own.  With the query blocks of one (batch, head) on consecutive workgroup ids its K / V rows were fetched from HBM

@@ -202,16 +202,10 @@ extern "C" int ppt_lnlin(const ppt_lnlin_params *pp, void *stream)
     if (p.dtype != PPT_BF16 && p.dtype != PPT_F16) return PPT_EINVAL;
     if (((uintptr_t)p.x | (uintptr_t)p.W | (uintptr_t)p.C | (uintptr_t)p.ln_w | (uintptr_t)p.ln_b | (uintptr_t)p.bias) & 15) return PPT_EINVAL;
     p.slices = p.N / NC;
-    static const int attrs_once = [] {
-        (void)hipFuncSetAttribute((const void *)lnlin_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute((const void *)lnlin_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        return 0;
-    }();
-    (void)attrs_once;
+    PPT_RAISE_LDS_ONCE(LDS_BYTES, (const void *)lnlin_kernel<bf16_t>, (const void *)lnlin_kernel<f16_t>);
     const int chunks = (p.M + R - 1) / R;
     const int grid = ((chunks + 7) / 8) * 8 * p.slices;                  // (chunk ids past the last return at once)
-    if (p.dtype == PPT_F16) hipLaunchKernelGGL(lnlin_kernel<f16_t>, dim3(grid), dim3(512), LDS_BYTES, ppt_stream(stream), p);
-    else hipLaunchKernelGGL(lnlin_kernel<bf16_t>, dim3(grid), dim3(512), LDS_BYTES, ppt_stream(stream), p);
+    ppt_launch16(p.dtype, [&](auto f) { hipLaunchKernelGGL(lnlin_kernel<decltype(f)>, dim3(grid), dim3(512), LDS_BYTES, ppt_stream(stream), p); });
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }

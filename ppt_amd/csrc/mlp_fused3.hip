@@ -475,12 +475,7 @@ extern "C" int ppt_vit_mlp3_bf16(const ppt_vit_mlp_params *pp, void *stream)
         if (!p.proj_W || (p.proj_row_scale && p.proj_row_scale_rows <= 0)) return PPT_EINVAL;
         if (((uintptr_t)p.proj_a | (uintptr_t)p.proj_W | (uintptr_t)p.proj_b) & 15) return PPT_EINVAL;
     }
-    static const int attrs_once = [] {
-        (void)hipFuncSetAttribute((const void *)vit_mlp3_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        (void)hipFuncSetAttribute((const void *)vit_mlp3_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        return 0;
-    }();
-    (void)attrs_once;
+    PPT_RAISE_LDS_ONCE(LDS_BYTES, (const void *)vit_mlp3_kernel<bf16_t>, (const void *)vit_mlp3_kernel<f16_t>);
     const int cus = ppt_cu_count(ppt_stream(stream));
     // chunks of at most R rows, a whole number of rounds over the CUs, every chunk as full as the division allows (mlp_fused.hip)
     int wgs = p.workgroups > 0 ? p.workgroups : cus;
@@ -491,8 +486,7 @@ extern "C" int ppt_vit_mlp3_bf16(const ppt_vit_mlp_params *pp, void *stream)
     p.rows_per_chunk = (p.M + p.n_chunks - 1) / p.n_chunks;
     p.n_chunks = (p.M + p.rows_per_chunk - 1) / p.rows_per_chunk;
     const int grid = p.n_chunks < wgs ? p.n_chunks : wgs;
-    if (p.dtype == PPT_F16) hipLaunchKernelGGL(vit_mlp3_kernel<f16_t>, dim3(grid), dim3(512), LDS_BYTES, ppt_stream(stream), p);
-    else hipLaunchKernelGGL(vit_mlp3_kernel<bf16_t>, dim3(grid), dim3(512), LDS_BYTES, ppt_stream(stream), p);
+    ppt_launch16(p.dtype, [&](auto f) { hipLaunchKernelGGL(vit_mlp3_kernel<decltype(f)>, dim3(grid), dim3(512), LDS_BYTES, ppt_stream(stream), p); });
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }

@@ -321,11 +321,7 @@ template <typename F, int K, bool LN, int EPI, int ACT>
 int launch(const ppt_rowgemm_params &p, hipStream_t s, int cus)
 {
     using G = RG<K>;
-    static const int once = [] {
-        (void)hipFuncSetAttribute((const void *)rowgemm_kernel<F, K, LN, EPI, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        return 0;
-    }();
-    (void)once;
+    PPT_RAISE_LDS_ONCE(G::LDS, (const void *)rowgemm_kernel<F, K, LN, EPI, ACT>);
     ppt_rowgemm_params q = p;
     q.groups = (p.N + G::NB - 1) / G::NB;
     const int tiles = (p.M + 31) / 32;

@@ -254,11 +254,7 @@ template <int NH, int FORM>
 void launch(const LinArgs &p, hipStream_t st)
 {
     constexpr int LDS_BYTES = LinForm<FORM>::PARTS * A_BYTES;
-    static const int attrs_once = [] {
-        (void)hipFuncSetAttribute((const void *)text_lin_kernel<NH, FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        return 0;
-    }();
-    (void)attrs_once;
+    PPT_RAISE_LDS_ONCE(LDS_BYTES, (const void *)text_lin_kernel<NH, FORM>);
     const int grid = (p.N / (128 * NH)) * (p.K / KC) * ((p.M + R - 1) / R);
     hipLaunchKernelGGL((text_lin_kernel<NH, FORM>), dim3(grid), dim3(512), LDS_BYTES, st, p);
 }

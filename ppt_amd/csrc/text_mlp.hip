@@ -392,13 +392,8 @@ int launch(const ppt_text_mlp_params &p, void *stream)
     constexpr bool LN_OK = S::R == 32;                                   // the LayerNorm prologue: 16 threads per row x 32 rows
     const bool ln = p.ln_w != nullptr;
     if (ln && !LN_OK) return PPT_EINVAL;
-    static const int attrs_once = [] {
-        (void)hipFuncSetAttribute((const void *)text_mlp_kernel<FORM, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS_BYTES);
-        (void)hipFuncSetAttribute((const void *)text_mlp_kernel<FORM, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS_BYTES);
-        (void)hipFuncSetAttribute((const void *)text_mlp_kernel<FORM, 0, LN_OK>, hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS_BYTES);
-        return 0;
-    }();
-    (void)attrs_once;
+    PPT_RAISE_LDS_ONCE(S::LDS_BYTES, (const void *)text_mlp_kernel<FORM, 0, false>, (const void *)text_mlp_kernel<FORM, 1, false>,
+                       (const void *)text_mlp_kernel<FORM, 0, LN_OK>);
     const dim3 grid(NS * ((p.M + S::R - 1) / S::R)), block(512);
     hipStream_t st = ppt_stream(stream);
     if (ln) hipLaunchKernelGGL((text_mlp_kernel<FORM, 0, LN_OK>), grid, block, S::LDS_BYTES, st, p);
