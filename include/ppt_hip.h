@@ -48,7 +48,8 @@ const char *ppt_strerror(int code);
  *    ppt_text_mlp_retile_split + the split16 fields of ppt_text_mlp_params (csrc/text_mlp.hip), ppt_text_lin_split /
  *    ppt_text_lin_retile_split (csrc/text_lin.hip); later, additive only (no existing signature or struct changed):
  *    ppt_text_lin16 / ppt_text_lin_retile16 (the 16-bit form of ppt_text_lin_split); ppt_cloud_prep_f32 / ppt_cloud_draws (csrc/cloud_prep.hip);
- *    ppt_cls_metrics / ppt_partseg_metrics / ppt_partseg_metrics_chunks (csrc/metrics.hip).
+ *    ppt_cls_metrics / ppt_partseg_metrics / ppt_partseg_metrics_chunks (csrc/metrics.hip);
+ *    ppt_logreg_fit_f32 / ppt_logreg_predict_f32 / ppt_logreg_workspace_bytes (csrc/logreg.hip).
  * 6: ppt_gemm_params.split16 / split_a_pow2 / split_b_pow2 (new trailing fields: fp32 operands as hi + lo half pairs),
  *    ppt_attention_fwd_split16 / ppt_attention_bwd_split16 (new), ppt_pointmlp_cloud_rstd / ppt_pointmlp_pq (new).
  * 5: ppt_labels_check (new), ppt_gemm256 (new: the 256-row macro-tile GEMM core), ppt_set_gemm256 / ppt_get_gemm256 (new),
@@ -801,6 +802,40 @@ int ppt_partseg_metrics_chunks(int N);
 int ppt_partseg_metrics(const float *logits, const int64_t *labels, float smoothing, int B, int N, int P,
                         const int32_t *part_start, const int32_t *part_count, int max_parts, int32_t *records, float *partial,
                         void *stream);
+
+/* ---- few-shot linear probe (ABI 7, additive; csrc/logreg.hip; host side: ppt_amd/probe.py) ------------------------------------
+ * What the reference's linear_probe.py:55,68,73 asks of sklearn.LogisticRegression(solver="lbfgs", penalty="l2", C=c).fit and
+ * .predict, for F independent fits in one launch: one persistent workgroup per fit, no communication between workgroups, no
+ * atomics, a fixed summation order (two runs write identical bytes; a fit's bytes do not depend on its neighbours in the launch).
+ *
+ * logreg_fit: fit f minimises over W [K, d] and an unpenalised intercept b [K], from zero,
+ *     F(W, b) = sum_i ( logsumexp_k z_ik - z_{i, y_i} ) + ||W||^2 / (2 C[f]),   z_i = W x_i + b,
+ *   x_i = feat[rows[f, i], 0:d], y_i = labels[rows[f, i]], i < n, by L-BFGS (10 pairs, Armijo backtracking with c1 = 1e-4, first
+ *   trial step 1 / ||g||_2 while the history is empty and 1 otherwise, pairs with s.y <= eps * y.y skipped; at the start and after
+ *   every accepted step the intercept takes the exact iterative-scaling step b_k += log(n_k / sum_i softmax(z_i)_k), which keeps
+ *   grad_b F at round-off), all in fp32.  It stops
+ *   at max |grad (F / n)| <= tol or after max_iter iterations.
+ *   feat [Nbank, ld] f32 (ld >= d), labels [Nbank] i64, rows [F, n] i32; C [F]: a HOST array (the values travel by value with the
+ *   launch, so the call stays capturable), every entry finite and > 0.
+ *   -> W [F, K, d], b [F, K] f32, info [F, PPT_LOGREG_INFO] i32, per fit:
+ *     [0] iterations   [1] evaluations of F (line-search trials and intercept steps)   [2] status: PPT_LOGREG_CONVERGED, _MAXITER, _LINESEARCH (no step decreased F: the
+ *     last, i.e. best, iterate is returned) or _BADINPUT (a selected row outside [0, Nbank) or its label outside [0, K): W, b zero,
+ *     nothing read out of bounds)   [3] the bits of the final max |grad (F / n)|   [4] the bits of the final F / n   [5..7] zero.
+ *   workspace: ppt_logreg_workspace_bytes(F, n, d, K) bytes, 256-byte aligned (0 for an unsupported shape).
+ *   2 <= K <= 64, 1 <= d <= 1024, K <= n <= 1024: PPT_EUNSUPPORTED outside (nothing launched).
+ * logreg_predict: pred[f, i] = the first arg-max over k of W[f, k] . feat[rows[i], 0:d] + b[f, k] (clf.predict; fp32 FMAs only), for
+ *   all F fits over the same rows [n_eval] i32 (NULL: rows 0 .. n_eval - 1).  pred [F, n_eval] i32; -1 for a row outside the bank. */
+#define PPT_LOGREG_INFO 8
+#define PPT_LOGREG_CONVERGED 0
+#define PPT_LOGREG_MAXITER 1
+#define PPT_LOGREG_LINESEARCH 2
+#define PPT_LOGREG_BADINPUT 3
+size_t ppt_logreg_workspace_bytes(int F, int n, int d, int K);
+int ppt_logreg_fit_f32(const float *feat, int64_t ld, int Nbank, const int64_t *labels, const int32_t *rows, int F, int n, int d,
+                       int K, const float *C, float tol, int max_iter, float *W, float *b, int32_t *info, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int ppt_logreg_predict_f32(const float *feat, int64_t ld, int Nbank, const int32_t *rows, int n_eval, const float *W,
+                           const float *b, int F, int d, int K, int32_t *pred, void *stream);
 
 #ifdef __cplusplus
 }

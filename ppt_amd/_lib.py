@@ -245,6 +245,11 @@ _SIGNATURES = {
     "ppt_partseg_metrics_chunks": (c_int, [c_int]),
     "ppt_partseg_metrics": (c_int, [c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                     c_void_p]),
+    "ppt_logreg_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
+    "ppt_logreg_fit_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_float),
+                                   c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    "ppt_logreg_predict_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                       c_void_p]),
 }
 
 

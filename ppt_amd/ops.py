@@ -1281,6 +1281,58 @@ def partseg_metrics(logits, labels, smoothing, part_start, part_count, max_parts
                                               int(max_parts), _p(records), _p(partial), _stream()), "ppt_partseg_metrics")
 
 
+LOGREG_INFO = 8                                     # words of a fit's info record (include/ppt_hip.h)
+LOGREG_CONVERGED, LOGREG_MAXITER, LOGREG_LINESEARCH, LOGREG_BADINPUT = 0, 1, 2, 3
+
+
+def _bank(feat, d):
+    """(ld, Nbank) of a feature bank [Nbank, >= d] f32 whose rows may be padded (row stride >= d, unit column stride)."""
+    if not feat.is_cuda or feat.dtype != torch.float32 or feat.dim() != 2 or feat.stride(1) != 1 or feat.stride(0) < d or feat.shape[1] < d:
+        raise RuntimeError("feature bank: expected a CUDA/HIP f32 matrix [N, >= d] with contiguous rows")
+    return feat.stride(0), feat.shape[0]
+
+
+def logreg_fit(feat, labels, rows, C, K, d=None, tol=1e-4, max_iter=1000, workspace=None):
+    """F independent L2-regularised multinomial logistic regressions in one launch (ppt_logreg_fit_f32): fit f uses the rows
+    rows[f] (int32 [F, n]) of the bank feat [Nbank, ld] f32 with labels [Nbank] i64 and the weight C[f] (a host sequence).
+    -> (W [F, K, d] f32, b [F, K] f32, info [F, 8] i32: iterations, evaluations, status, the bits of max |grad F / n| and of
+    F / n).  workspace: a caller-owned uint8 tensor of at least logreg_workspace_bytes(F, n, d, K) bytes (allocated when None)."""
+    d = feat.shape[1] if d is None else int(d)
+    ld, Nbank = _bank(feat, d)
+    _chk(labels, torch.int64, "labels"); _chk(rows, torch.int32, "rows")
+    F, n = rows.shape
+    Cs = [float(c) for c in C]
+    assert len(Cs) == F and labels.numel() == Nbank
+    need = _lib.lib().ppt_logreg_workspace_bytes(F, n, d, int(K))
+    if workspace is None:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=feat.device)
+    W = torch.empty((F, K, d), dtype=torch.float32, device=feat.device)
+    b = torch.empty((F, K), dtype=torch.float32, device=feat.device)
+    info = torch.empty((F, LOGREG_INFO), dtype=torch.int32, device=feat.device)
+    _lib.check(_lib.lib().ppt_logreg_fit_f32(_p(feat), ld, Nbank, _p(labels), _p(rows), F, n, d, int(K), (_lib.c_float * F)(*Cs),
+                                             float(tol), int(max_iter), _p(W), _p(b), _p(info), _p(workspace), workspace.numel(),
+                                             _stream()), "ppt_logreg_fit_f32")
+    return W, b, info
+
+
+def logreg_workspace_bytes(F, n, d, K):
+    """bytes of scratch ppt_logreg_fit_f32 needs for F fits of n rows, d features, K classes (0: unsupported shape)"""
+    return _lib.lib().ppt_logreg_workspace_bytes(int(F), int(n), int(d), int(K))
+
+
+def logreg_predict(feat, W, b, rows=None):
+    """pred[f, i] = first arg-max over k of W[f, k] . feat[rows[i]] + b[f, k], in fp32 (ppt_logreg_predict_f32).  feat [Nbank, ld]
+    f32, W [F, K, d], b [F, K], rows int32 [n_eval] or None (the whole bank) -> pred [F, n_eval] i32 (-1: row outside the bank)."""
+    _chk(W, torch.float32, "W"); _chk(b, torch.float32, "b"); _chk(rows, torch.int32, "rows")
+    F, K, d = W.shape
+    ld, Nbank = _bank(feat, d)
+    n_eval = Nbank if rows is None else rows.numel()
+    pred = torch.empty((F, n_eval), dtype=torch.int32, device=feat.device)
+    _lib.check(_lib.lib().ppt_logreg_predict_f32(_p(feat), ld, Nbank, _p(rows), n_eval, _p(W), _p(b), F, d, K, _p(pred), _stream()),
+               "ppt_logreg_predict_f32")
+    return pred
+
+
 def health_check(x, flags, bit, maxabs=None):
     """flags[0] |= bit if x (any dtype, contiguous) holds a non-finite value; maxabs[0] = max(maxabs[0], max |finite x|) when
     given (ppt_health_check).  flags: int32 [1]; maxabs: f32 [1], non-negative."""
