@@ -308,38 +308,11 @@ __global__ __launch_bounds__(256) void weights_prep_kernel(const wprep_table tb)
         }
 }
 
-template <typename TS>
-int convert_from(const void *src, void *dst, int dd, int64_t n, float scale, hipStream_t s)
+// fn(TS{}, TD{}) for a (source, destination) pair of format codes: ppt_launch3 nested; false when either code is none of the three.
+template <typename Fn> bool launch_pair(int src_dtype, int dst_dtype, Fn &&fn)
 {
-    if constexpr (sizeof(TS) == 4) {
-        if ((dd == PPT_BF16 || dd == PPT_F16) && (n & 7) == 0 && ((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0) {
-            const int64_t n8 = n >> 3;
-            const unsigned grid8 = (unsigned)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
-            if (dd == PPT_BF16) hipLaunchKernelGGL(convert8_kernel<bf16_t>, dim3(grid8), dim3(256), 0, s, (const float *)src, (bf16_t *)dst, n8, scale);
-            else hipLaunchKernelGGL(convert8_kernel<f16_t>, dim3(grid8), dim3(256), 0, s, (const float *)src, (f16_t *)dst, n8, scale);
-            PPT_CHECK_LAUNCH();
-            return PPT_OK;
-        }
-    }
-    const unsigned grid = (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-    if (dd == PPT_BF16) hipLaunchKernelGGL((convert_kernel<TS, bf16_t>), dim3(grid), dim3(256), 0, s, (const TS *)src, (bf16_t *)dst, n, scale);
-    else if (dd == PPT_F16) hipLaunchKernelGGL((convert_kernel<TS, f16_t>), dim3(grid), dim3(256), 0, s, (const TS *)src, (f16_t *)dst, n, scale);
-    else if (dd == PPT_F32) hipLaunchKernelGGL((convert_kernel<TS, float>), dim3(grid), dim3(256), 0, s, (const TS *)src, (float *)dst, n, scale);
-    else return PPT_EINVAL;
-    PPT_CHECK_LAUNCH();
-    return PPT_OK;
-}
-
-template <typename TS>
-int transpose_from(const void *src, void *dst, int dd, int rows, int cols, int64_t ldd, hipStream_t s)
-{
-    dim3 grid((cols + 31) / 32, (rows + 31) / 32);
-    if (dd == PPT_BF16) hipLaunchKernelGGL((transpose_kernel<TS, bf16_t>), grid, dim3(256), 0, s, (const TS *)src, (bf16_t *)dst, rows, cols, ldd);
-    else if (dd == PPT_F16) hipLaunchKernelGGL((transpose_kernel<TS, f16_t>), grid, dim3(256), 0, s, (const TS *)src, (f16_t *)dst, rows, cols, ldd);
-    else if (dd == PPT_F32) hipLaunchKernelGGL((transpose_kernel<TS, float>), grid, dim3(256), 0, s, (const TS *)src, (float *)dst, rows, cols, ldd);
-    else return PPT_EINVAL;
-    PPT_CHECK_LAUNCH();
-    return PPT_OK;
+    bool dst_ok = false;
+    return ppt_launch3(src_dtype, [&](auto ts) { dst_ok = ppt_launch3(dst_dtype, [&](auto td) { fn(ts, td); }); }) && dst_ok;
 }
 
 }  // namespace
@@ -347,13 +320,10 @@ int transpose_from(const void *src, void *dst, int dd, int rows, int cols, int64
 extern "C" int ppt_cls_max_pool(const void *x, int x_dtype, int B, int T, int D, float *out, int32_t *argmax, void *stream)
 {
     if (!x || !out || B <= 0 || T < 2 || D <= 0) return PPT_EINVAL;
-    if (x_dtype == PPT_F32)
-        hipLaunchKernelGGL(cls_max_pool_kernel<float>, dim3((D + 63) / 64, B), dim3(CMP_W * 64), 0, ppt_stream(stream), (const float *)x, T, D, out, argmax);
-    else if (x_dtype == PPT_BF16)
-        hipLaunchKernelGGL(cls_max_pool_kernel<bf16_t>, dim3((D + 63) / 64, B), dim3(CMP_W * 64), 0, ppt_stream(stream), (const bf16_t *)x, T, D, out, argmax);
-    else if (x_dtype == PPT_F16)
-        hipLaunchKernelGGL(cls_max_pool_kernel<f16_t>, dim3((D + 63) / 64, B), dim3(CMP_W * 64), 0, ppt_stream(stream), (const f16_t *)x, T, D, out, argmax);
-    else
+    if (!ppt_launch3(x_dtype, [&](auto t) {
+            using TX = decltype(t);
+            hipLaunchKernelGGL(cls_max_pool_kernel<TX>, dim3((D + 63) / 64, B), dim3(CMP_W * 64), 0, ppt_stream(stream), (const TX *)x, T, D, out, argmax);
+        }))
         return PPT_EINVAL;
     PPT_CHECK_LAUNCH();
     return PPT_OK;
@@ -378,9 +348,8 @@ extern "C" int ppt_weights_prep(const ppt_wprep_item *items, int count, int dtyp
             if (blocks > 0x7fffffff) return PPT_EUNSUPPORTED;
         }
         tb.first_block[tb.count] = (int)blocks;
-        if (dtype == PPT_F16) hipLaunchKernelGGL(weights_prep_kernel<f16_t>, dim3((unsigned)blocks), dim3(256), 0, ppt_stream(stream), tb);
-        else if (dtype == PPT_F32) hipLaunchKernelGGL(weights_prep_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, ppt_stream(stream), tb);   // (fp32 / split16 modes)
-        else hipLaunchKernelGGL(weights_prep_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, ppt_stream(stream), tb);
+        // (dtype was checked above; float: the fp32 / split16 modes)
+        (void)ppt_launch3(dtype, [&](auto t) { hipLaunchKernelGGL(weights_prep_kernel<decltype(t)>, dim3((unsigned)blocks), dim3(256), 0, ppt_stream(stream), tb); });
         PPT_CHECK_LAUNCH();
     }
     return PPT_OK;
@@ -390,10 +359,11 @@ extern "C" int ppt_health_check(const void *x, int x_dtype, int64_t n, uint32_t 
 {
     if (!x || !flags || n <= 0) return PPT_EINVAL;
     const unsigned grid = (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-    if (x_dtype == PPT_F32) hipLaunchKernelGGL(health_check_kernel<float>, dim3(grid), dim3(256), 0, ppt_stream(stream), (const float *)x, n, flags, bit, maxabs);
-    else if (x_dtype == PPT_BF16) hipLaunchKernelGGL(health_check_kernel<bf16_t>, dim3(grid), dim3(256), 0, ppt_stream(stream), (const bf16_t *)x, n, flags, bit, maxabs);
-    else if (x_dtype == PPT_F16) hipLaunchKernelGGL(health_check_kernel<f16_t>, dim3(grid), dim3(256), 0, ppt_stream(stream), (const f16_t *)x, n, flags, bit, maxabs);
-    else return PPT_EINVAL;
+    if (!ppt_launch3(x_dtype, [&](auto t) {
+            using TS = decltype(t);
+            hipLaunchKernelGGL(health_check_kernel<TS>, dim3(grid), dim3(256), 0, ppt_stream(stream), (const TS *)x, n, flags, bit, maxabs);
+        }))
+        return PPT_EINVAL;
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }
@@ -413,13 +383,10 @@ extern "C" int ppt_scale_rows_convert(const float *W, int64_t ldw, int N, int K,
     if (!W || !scale || !out || N <= 0 || K <= 0 || (K & 3) || ldw < K || (ldw & 3)) return PPT_EINVAL;
     if ((((uintptr_t)W) | ((uintptr_t)out)) & 15) return PPT_EINVAL;
     const unsigned grid = (unsigned)(((int64_t)N * (K / 4) + 255) / 256);
-    if (out_dtype == PPT_BF16)
-        hipLaunchKernelGGL(scale_rows_convert_kernel<bf16_t>, dim3(grid), dim3(256), 0, ppt_stream(stream), W, ldw, N, K, scale, (bf16_t *)out, b, shift, bs);
-    else if (out_dtype == PPT_F16)
-        hipLaunchKernelGGL(scale_rows_convert_kernel<f16_t>, dim3(grid), dim3(256), 0, ppt_stream(stream), W, ldw, N, K, scale, (f16_t *)out, b, shift, bs);
-    else if (out_dtype == PPT_F32)
-        hipLaunchKernelGGL(scale_rows_convert_kernel<float>, dim3(grid), dim3(256), 0, ppt_stream(stream), W, ldw, N, K, scale, (float *)out, b, shift, bs);
-    else
+    if (!ppt_launch3(out_dtype, [&](auto t) {
+            using TD = decltype(t);
+            hipLaunchKernelGGL(scale_rows_convert_kernel<TD>, dim3(grid), dim3(256), 0, ppt_stream(stream), W, ldw, N, K, scale, (TD *)out, b, shift, bs);
+        }))
         return PPT_EINVAL;
     PPT_CHECK_LAUNCH();
     return PPT_OK;
@@ -428,10 +395,26 @@ extern "C" int ppt_scale_rows_convert(const float *W, int64_t ldw, int N, int K,
 extern "C" int ppt_convert_scaled(const void *src, int src_dtype, void *dst, int dst_dtype, int64_t n, float scale, void *stream)
 {
     if (!src || !dst || n <= 0 || !(scale > 0.f)) return PPT_EINVAL;
-    if (src_dtype == PPT_F32) return convert_from<float>(src, dst, dst_dtype, n, scale, ppt_stream(stream));
-    if (src_dtype == PPT_BF16) return convert_from<bf16_t>(src, dst, dst_dtype, n, scale, ppt_stream(stream));
-    if (src_dtype == PPT_F16) return convert_from<f16_t>(src, dst, dst_dtype, n, scale, ppt_stream(stream));
-    return PPT_EINVAL;
+    if (src_dtype == PPT_F32 && (dst_dtype == PPT_BF16 || dst_dtype == PPT_F16) && (n & 7) == 0 &&
+        ((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0) {
+        const int64_t n8 = n >> 3;
+        const unsigned grid8 = (unsigned)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
+        ppt_launch16(dst_dtype, [&](auto t) {
+            using TD = decltype(t);
+            hipLaunchKernelGGL(convert8_kernel<TD>, dim3(grid8), dim3(256), 0, ppt_stream(stream), (const float *)src, (TD *)dst, n8, scale);
+        });
+        PPT_CHECK_LAUNCH();
+        return PPT_OK;
+    }
+    const unsigned grid = (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+    if (!launch_pair(src_dtype, dst_dtype, [&](auto ts, auto td) {
+            using TS = decltype(ts);
+            using TD = decltype(td);
+            hipLaunchKernelGGL((convert_kernel<TS, TD>), dim3(grid), dim3(256), 0, ppt_stream(stream), (const TS *)src, (TD *)dst, n, scale);
+        }))
+        return PPT_EINVAL;
+    PPT_CHECK_LAUNCH();
+    return PPT_OK;
 }
 
 extern "C" int ppt_convert(const void *src, int src_dtype, void *dst, int dst_dtype, int64_t n, void *stream)
@@ -443,10 +426,15 @@ extern "C" int ppt_transpose(const void *src, int src_dtype, void *dst, int dst_
                              void *stream)
 {
     if (!src || !dst || rows <= 0 || cols <= 0 || ld_dst < rows) return PPT_EINVAL;
-    if (src_dtype == PPT_F32) return transpose_from<float>(src, dst, dst_dtype, rows, cols, ld_dst, ppt_stream(stream));
-    if (src_dtype == PPT_BF16) return transpose_from<bf16_t>(src, dst, dst_dtype, rows, cols, ld_dst, ppt_stream(stream));
-    if (src_dtype == PPT_F16) return transpose_from<f16_t>(src, dst, dst_dtype, rows, cols, ld_dst, ppt_stream(stream));
-    return PPT_EINVAL;
+    dim3 grid((cols + 31) / 32, (rows + 31) / 32);
+    if (!launch_pair(src_dtype, dst_dtype, [&](auto ts, auto td) {
+            using TS = decltype(ts);
+            using TD = decltype(td);
+            hipLaunchKernelGGL((transpose_kernel<TS, TD>), grid, dim3(256), 0, ppt_stream(stream), (const TS *)src, (TD *)dst, rows, cols, ld_dst);
+        }))
+        return PPT_EINVAL;
+    PPT_CHECK_LAUNCH();
+    return PPT_OK;
 }
 
 extern "C" int ppt_col_sums(const void *x, int x_dtype, int M, int D, int64_t ldx, float *partial, void *stream)
@@ -456,19 +444,15 @@ extern "C" int ppt_col_sums(const void *x, int x_dtype, int M, int D, int64_t ld
     if (x_dtype == PPT_F32 && D % 4 == 0 && ldx % 4 == 0 && !(((uintptr_t)x | (uintptr_t)partial) & 15))
         hipLaunchKernelGGL(col_sums_vec_kernel, dim3((D + 63) / 64, (M + 255) / 256), dim3(256), 0, ppt_stream(stream),
                            (const float *)x, M, D, ldx, partial);
-    else if (x_dtype == PPT_F32)
-        hipLaunchKernelGGL(col_sums_kernel<float>, grid, dim3(256), 0, ppt_stream(stream), (const float *)x, M, D, ldx, partial);
-    else if (x_dtype == PPT_BF16 && D % 8 == 0 && ldx % 8 == 0 && !((uintptr_t)x & 15))
-        hipLaunchKernelGGL(col_sums_vec8_bf16_kernel<bf16_t>, dim3((D + 127) / 128, (M + 255) / 256), dim3(256), 0, ppt_stream(stream),
-                           (const bf16_t *)x, M, D, ldx, partial);
-    else if (x_dtype == PPT_F16 && D % 8 == 0 && ldx % 8 == 0 && !((uintptr_t)x & 15))
-        hipLaunchKernelGGL(col_sums_vec8_bf16_kernel<f16_t>, dim3((D + 127) / 128, (M + 255) / 256), dim3(256), 0, ppt_stream(stream),
-                           (const bf16_t *)x, M, D, ldx, partial);
-    else if (x_dtype == PPT_BF16)
-        hipLaunchKernelGGL(col_sums_kernel<bf16_t>, grid, dim3(256), 0, ppt_stream(stream), (const bf16_t *)x, M, D, ldx, partial);
-    else if (x_dtype == PPT_F16)
-        hipLaunchKernelGGL(col_sums_kernel<f16_t>, grid, dim3(256), 0, ppt_stream(stream), (const f16_t *)x, M, D, ldx, partial);
-    else
+    else if ((x_dtype == PPT_BF16 || x_dtype == PPT_F16) && D % 8 == 0 && ldx % 8 == 0 && !((uintptr_t)x & 15))
+        ppt_launch16(x_dtype, [&](auto f) {
+            hipLaunchKernelGGL(col_sums_vec8_bf16_kernel<decltype(f)>, dim3((D + 127) / 128, (M + 255) / 256), dim3(256), 0, ppt_stream(stream),
+                               (const bf16_t *)x, M, D, ldx, partial);
+        });
+    else if (!ppt_launch3(x_dtype, [&](auto t) {
+                 using TX = decltype(t);
+                 hipLaunchKernelGGL(col_sums_kernel<TX>, grid, dim3(256), 0, ppt_stream(stream), (const TX *)x, M, D, ldx, partial);
+             }))
         return PPT_EINVAL;
     PPT_CHECK_LAUNCH();
     return PPT_OK;

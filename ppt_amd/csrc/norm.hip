@@ -9,6 +9,29 @@ namespace {
 
 constexpr int MAX_EPL = 16;   // elements per lane -> D <= 1024
 
+// ---- the 8-columns-per-lane row (D % 8 == 0, D <= 512): a lane's eight consecutive fp32 values travel as two float4 (v0, v1) ------
+// Macros, because the two backward kernels keep their register allocation with nothing else: a function for any one of these
+// (float4 pair by reference, a two-float4 struct by value or by reference) changed ln_bwd_dx8_kernel and ln_bwd_w8_kernel; the
+// forward kernels took the struct-by-value form unchanged, but one vocabulary for the three kernels is worth more.  LOAD8 and
+// STORE8 name p twice and ADD8 binds it once, again because that is what leaves every kernel as it was (a bound pointer in LOAD8
+// or STORE8 changed the backward kernels, p twice in ADD8 the forward ones): pass them a pointer that is cheap to spell twice.
+#define LOAD8(p, v0, v1)                                                                                    \
+    do {                                                                                                     \
+        v0 = *reinterpret_cast<const float4 *>(p); v1 = *reinterpret_cast<const float4 *>((p) + 4);          \
+    } while (0)
+#define ADD8(p, v0, v1)                                                                                      \
+    do {                                                                                                     \
+        const float *p__ = (p);                                                                              \
+        const float4 a0__ = *reinterpret_cast<const float4 *>(p__), a1__ = *reinterpret_cast<const float4 *>(p__ + 4);                    \
+        v0.x += a0__.x; v0.y += a0__.y; v0.z += a0__.z; v0.w += a0__.w; v1.x += a1__.x; v1.y += a1__.y; v1.z += a1__.z; v1.w += a1__.w;   \
+    } while (0)
+#define UNPACK8(v0, v1) {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w}          // the initialiser of a float[8]
+#define STORE8(p, v)                                                                                         \
+    do {                                                                                                     \
+        *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);                                \
+        *reinterpret_cast<float4 *>((p) + 4) = make_float4(v[4], v[5], v[6], v[7]);                          \
+    } while (0)
+
 template <typename TY>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float *__restrict__ x, const float *__restrict__ add,
                                                      int add_rows, float *__restrict__ xs,
@@ -74,34 +97,20 @@ __global__ __launch_bounds__(256) void ln_fwd_vec8_kernel(const float *__restric
     const int nw = gridDim.x * 4;
     const bool on = lane * 8 < D;
     const int c = on ? lane * 8 : 0;
-    float g[8], be[8];
-    {
-        const float4 g0 = *reinterpret_cast<const float4 *>(w + c), g1 = *reinterpret_cast<const float4 *>(w + c + 4);
-        const float4 b0 = *reinterpret_cast<const float4 *>(b + c), b1 = *reinterpret_cast<const float4 *>(b + c + 4);
-        g[0] = g0.x; g[1] = g0.y; g[2] = g0.z; g[3] = g0.w; g[4] = g1.x; g[5] = g1.y; g[6] = g1.z; g[7] = g1.w;
-        be[0] = b0.x; be[1] = b0.y; be[2] = b0.z; be[3] = b0.w; be[4] = b1.x; be[5] = b1.y; be[6] = b1.z; be[7] = b1.w;
-    }
+    float4 g0, g1, b0, b1;
+    LOAD8(w + c, g0, g1);
+    LOAD8(b + c, b0, b1);
+    const float g[8] = UNPACK8(g0, g1), be[8] = UNPACK8(b0, b1);
     const float inv_d = 1.0f / (float)D;
     for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < M; row += nw) {
-        const float *xr = x + (size_t)row * D + c;
-        float4 v0 = *reinterpret_cast<const float4 *>(xr), v1 = *reinterpret_cast<const float4 *>(xr + 4);
-        if (add) {
-            const float *ar = add + (size_t)(add_rows > 0 ? row % add_rows : row) * D + c;
-            const float4 a0 = *reinterpret_cast<const float4 *>(ar), a1 = *reinterpret_cast<const float4 *>(ar + 4);
-            v0.x += a0.x; v0.y += a0.y; v0.z += a0.z; v0.w += a0.w; v1.x += a1.x; v1.y += a1.y; v1.z += a1.z; v1.w += a1.w;
-        }
+        float4 v0, v1;
+        LOAD8(x + (size_t)row * D + c, v0, v1);
+        if (add) ADD8(add + (size_t)(add_rows > 0 ? row % add_rows : row) * D + c, v0, v1);
         if constexpr (SUM) {
-            if (sum_bias) {
-                const float4 a0 = *reinterpret_cast<const float4 *>(sum_bias + c), a1 = *reinterpret_cast<const float4 *>(sum_bias + c + 4);
-                v0.x += a0.x; v0.y += a0.y; v0.z += a0.z; v0.w += a0.w; v1.x += a1.x; v1.y += a1.y; v1.z += a1.z; v1.w += a1.w;
-            }
-            for (int z = 0; z < S; ++z) {
-                const float *pr = parts + ((size_t)z * M + row) * D + c;
-                const float4 a0 = *reinterpret_cast<const float4 *>(pr), a1 = *reinterpret_cast<const float4 *>(pr + 4);
-                v0.x += a0.x; v0.y += a0.y; v0.z += a0.z; v0.w += a0.w; v1.x += a1.x; v1.y += a1.y; v1.z += a1.z; v1.w += a1.w;
-            }
+            if (sum_bias) ADD8(sum_bias + c, v0, v1);
+            for (int z = 0; z < S; ++z) ADD8(parts + ((size_t)z * M + row) * D + c, v0, v1);
         }
-        float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+        const float v[8] = UNPACK8(v0, v1);
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) s += v[j];
@@ -111,10 +120,7 @@ __global__ __launch_bounds__(256) void ln_fwd_vec8_kernel(const float *__restric
         for (int j = 0; j < 8; ++j) { const float d = v[j] - mean; q = fmaf(d, d, q); }
         const float rstd = 1.0f / sqrtf(wave_reduce_sum(on ? q : 0.f) * inv_d + eps);
         if (on) {
-            if (xs) {
-                *reinterpret_cast<float4 *>(xs + (size_t)row * D + c) = v0;
-                *reinterpret_cast<float4 *>(xs + (size_t)row * D + c + 4) = v1;
-            }
+            if (xs) STORE8(xs + (size_t)row * D + c, v);
             float o[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = (v[j] - mean) * rstd * g[j] + be[j];
@@ -122,8 +128,7 @@ __global__ __launch_bounds__(256) void ln_fwd_vec8_kernel(const float *__restric
                 *reinterpret_cast<uint4 *>(y + (size_t)row * D + c) =
                     make_uint4(h16<TY>::pack2(o[0], o[1]), h16<TY>::pack2(o[2], o[3]), h16<TY>::pack2(o[4], o[5]), h16<TY>::pack2(o[6], o[7]));
             } else {
-                *reinterpret_cast<float4 *>(y + (size_t)row * D + c) = make_float4(o[0], o[1], o[2], o[3]);
-                *reinterpret_cast<float4 *>(y + (size_t)row * D + c + 4) = make_float4(o[4], o[5], o[6], o[7]);
+                STORE8(y + (size_t)row * D + c, o);
             }
         }
         if (lane == 0) {
@@ -192,6 +197,38 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float *__restrict__ d
     }
 }
 
+// ---- the two pieces ln_bwd_dx8_kernel and ln_bwd_w8_kernel share, as macros in the kernel's scope for the reason given at LOAD8 ----
+// One row's arithmetic.  Reads dv, xv, wv (the lane's eight dy, x, gamma), mu, rs, act, D; declares gv, xh and the row means s1
+// (of g = dy * gamma) and s2 (of g * xhat).  PER_COLUMN runs for each j once xh[j] is known: ln_bwd_w8_kernel's dw / db sums.
+#define LN_BWD8_ROW(PER_COLUMN)                                                           \
+    float gv[8], xh[8], s1 = 0.f, s2 = 0.f;                                               \
+    _Pragma("unroll")                                                                     \
+    for (int j = 0; j < 8; ++j) {                                                         \
+        xh[j] = act ? (xv[j] - mu) * rs : 0.f;                                            \
+        PER_COLUMN;                                                                       \
+        gv[j] = dv[j] * wv[j];                                                            \
+        s1 += gv[j]; s2 += gv[j] * xh[j];                                                 \
+    }                                                                                     \
+    s1 = wave_reduce_sum(s1) / (float)D;                                                  \
+    s2 = wave_reduce_sum(s2) / (float)D
+// The lane's eight dx at element offset `off` (added to av, the row of dx loaded before: zeros unless accumulate) and their fp32 or
+// 16-bit operand copy: one 16-byte store per lane for the latter.  Reads av, rs, gv, xh, s1, s2, dx, dx_copy, copy_dtype.
+#define LN_BWD8_STORE_DX(off)                                                                                                     \
+    do {                                                                                                                          \
+        float t[8];                                                                                                               \
+        _Pragma("unroll")                                                                                                         \
+        for (int j = 0; j < 8; ++j) t[j] = av[j] + rs * (gv[j] - s1 - xh[j] * s2);                                                \
+        STORE8(dx + (off), t);                                                                                                    \
+        if (dx_copy) {                                                                                                            \
+            if (copy_dtype != PPT_F32) {                                                                                          \
+                *reinterpret_cast<uint4 *>((uint16_t *)dx_copy + (off)) = make_uint4(pack2_dt(copy_dtype, t[0], t[1]), pack2_dt(copy_dtype, t[2], t[3]), \
+                                                                                   pack2_dt(copy_dtype, t[4], t[5]), pack2_dt(copy_dtype, t[6], t[7])); \
+            } else {                                                                                                              \
+                STORE8((float *)dx_copy + (off), t);                                                                              \
+            }                                                                                                                     \
+        }                                                                                                                         \
+    } while (0)
+
 // The input-gradient-only backward (no dw / db: the text tower's LayerNorms are frozen) for D % 8 == 0, D <= 512: one wave per
 // row, a lane owns EIGHT consecutive columns -- two 16-byte loads per tensor, and the row of dx that the result is added to is
 // requested together with dy and xs instead of after the reduction (the scalar kernel's third dependent round trip); the bf16
@@ -210,43 +247,17 @@ __global__ __launch_bounds__(256) void ln_bwd_dx8_kernel(const float *__restrict
     const size_t off = (size_t)row * D + lane * 8;
     float4 d0 = make_float4(0.f, 0.f, 0.f, 0.f), d1 = d0, x0 = d0, x1 = d0, a0 = d0, a1 = d0, w0 = d0, w1 = d0;
     if (act) {
-        d0 = *reinterpret_cast<const float4 *>(dy + off); d1 = *reinterpret_cast<const float4 *>(dy + off + 4);
-        for (int z = 1; z < S; ++z) {
-            const float *pr = dy + (size_t)z * M * D + off;
-            const float4 e0 = *reinterpret_cast<const float4 *>(pr), e1 = *reinterpret_cast<const float4 *>(pr + 4);
-            d0.x += e0.x; d0.y += e0.y; d0.z += e0.z; d0.w += e0.w; d1.x += e1.x; d1.y += e1.y; d1.z += e1.z; d1.w += e1.w;
-        }
-        x0 = *reinterpret_cast<const float4 *>(xs + off); x1 = *reinterpret_cast<const float4 *>(xs + off + 4);
-        w0 = *reinterpret_cast<const float4 *>(w + lane * 8); w1 = *reinterpret_cast<const float4 *>(w + lane * 8 + 4);
-        if (accumulate) { a0 = *reinterpret_cast<const float4 *>(dx + off); a1 = *reinterpret_cast<const float4 *>(dx + off + 4); }
+        LOAD8(dy + off, d0, d1);
+        for (int z = 1; z < S; ++z) ADD8(dy + (size_t)z * M * D + off, d0, d1);
+        LOAD8(xs + off, x0, x1);
+        LOAD8(w + lane * 8, w0, w1);
+        if (accumulate) LOAD8(dx + off, a0, a1);
     }
     const float mu = mean[row], rs = rstd[row];
-    const float dv[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w}, xv[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-    const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w}, av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-    float gv[8], xh[8], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        xh[j] = act ? (xv[j] - mu) * rs : 0.f;
-        gv[j] = dv[j] * wv[j];
-        s1 += gv[j]; s2 += gv[j] * xh[j];
-    }
-    s1 = wave_reduce_sum(s1) / (float)D;
-    s2 = wave_reduce_sum(s2) / (float)D;
+    const float dv[8] = UNPACK8(d0, d1), xv[8] = UNPACK8(x0, x1), wv[8] = UNPACK8(w0, w1), av[8] = UNPACK8(a0, a1);
+    LN_BWD8_ROW((void)0);
     if (!act) return;
-    float t[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t[j] = av[j] + rs * (gv[j] - s1 - xh[j] * s2);
-    *reinterpret_cast<float4 *>(dx + off) = make_float4(t[0], t[1], t[2], t[3]);
-    *reinterpret_cast<float4 *>(dx + off + 4) = make_float4(t[4], t[5], t[6], t[7]);
-    if (dx_copy) {
-        if (copy_dtype != PPT_F32) {
-            *reinterpret_cast<uint4 *>((uint16_t *)dx_copy + off) = make_uint4(pack2_dt(copy_dtype, t[0], t[1]), pack2_dt(copy_dtype, t[2], t[3]),
-                                                                               pack2_dt(copy_dtype, t[4], t[5]), pack2_dt(copy_dtype, t[6], t[7]));
-        } else {
-            *reinterpret_cast<float4 *>((float *)dx_copy + off) = make_float4(t[0], t[1], t[2], t[3]);
-            *reinterpret_cast<float4 *>((float *)dx_copy + off + 4) = make_float4(t[4], t[5], t[6], t[7]);
-        }
-    }
+    LN_BWD8_STORE_DX(off);
 }
 
 // The backward WITH weight / bias gradients (trainable LayerNorms: the un-frozen last PointBERT block, point_encoder.py:70-79) in
@@ -269,8 +280,8 @@ __global__ __launch_bounds__(256) void ln_bwd_w8_kernel(const float *__restrict_
     const bool act = lane * 8 < D;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 w0 = z4, w1 = z4;
-    if (act) { w0 = *reinterpret_cast<const float4 *>(w + lane * 8); w1 = *reinterpret_cast<const float4 *>(w + lane * 8 + 4); }
-    const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+    if (act) LOAD8(w + lane * 8, w0, w1);
+    const float wv[8] = UNPACK8(w0, w1);
     float dwa[8], dba[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { dwa[j] = 0.f; dba[j] = 0.f; }
@@ -278,9 +289,9 @@ __global__ __launch_bounds__(256) void ln_bwd_w8_kernel(const float *__restrict_
     auto fetch = [&](int row, float4 &D0, float4 &D1, float4 &X0, float4 &X1, float4 &A0, float4 &A1) {
         if (act) {
             const size_t off = (size_t)row * D + lane * 8;
-            D0 = *reinterpret_cast<const float4 *>(dy + off); D1 = *reinterpret_cast<const float4 *>(dy + off + 4);
-            X0 = *reinterpret_cast<const float4 *>(xs + off); X1 = *reinterpret_cast<const float4 *>(xs + off + 4);
-            if (accumulate) { A0 = *reinterpret_cast<const float4 *>(dx + off); A1 = *reinterpret_cast<const float4 *>(dx + off + 4); }
+            LOAD8(dy + off, D0, D1);
+            LOAD8(xs + off, X0, X1);
+            if (accumulate) LOAD8(dx + off, A0, A1);
         }
     };
     fetch(r0, d0, d1, x0, x1, a0, a1);
@@ -288,44 +299,48 @@ __global__ __launch_bounds__(256) void ln_bwd_w8_kernel(const float *__restrict_
         float4 nd0 = z4, nd1 = z4, nx0 = z4, nx1 = z4, na0 = z4, na1 = z4;
         if (row + 1 < r1) fetch(row + 1, nd0, nd1, nx0, nx1, na0, na1);       // in flight during this row's reductions
         const float mu = mean[row], rs = rstd[row];
-        const float dv[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w}, xv[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-        const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-        float gv[8], xh[8], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            xh[j] = act ? (xv[j] - mu) * rs : 0.f;
-            dwa[j] += dv[j] * xh[j]; dba[j] += dv[j];
-            gv[j] = dv[j] * wv[j];
-            s1 += gv[j]; s2 += gv[j] * xh[j];
-        }
-        s1 = wave_reduce_sum(s1) / (float)D;
-        s2 = wave_reduce_sum(s2) / (float)D;
+        const float dv[8] = UNPACK8(d0, d1), xv[8] = UNPACK8(x0, x1), av[8] = UNPACK8(a0, a1);
+        LN_BWD8_ROW(dwa[j] += dv[j] * xh[j]; dba[j] += dv[j]);
         if (act) {
             const size_t off = (size_t)row * D + lane * 8;
-            float t[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) t[j] = av[j] + rs * (gv[j] - s1 - xh[j] * s2);
-            *reinterpret_cast<float4 *>(dx + off) = make_float4(t[0], t[1], t[2], t[3]);
-            *reinterpret_cast<float4 *>(dx + off + 4) = make_float4(t[4], t[5], t[6], t[7]);
-            if (dx_copy) {
-                if (copy_dtype != PPT_F32) {
-                    *reinterpret_cast<uint4 *>((uint16_t *)dx_copy + off) = make_uint4(pack2_dt(copy_dtype, t[0], t[1]), pack2_dt(copy_dtype, t[2], t[3]),
-                                                                                       pack2_dt(copy_dtype, t[4], t[5]), pack2_dt(copy_dtype, t[6], t[7]));
-                } else {
-                    *reinterpret_cast<float4 *>((float *)dx_copy + off) = make_float4(t[0], t[1], t[2], t[3]);
-                    *reinterpret_cast<float4 *>((float *)dx_copy + off + 4) = make_float4(t[4], t[5], t[6], t[7]);
-                }
-            }
+            LN_BWD8_STORE_DX(off);
         }
         d0 = nd0; d1 = nd1; x0 = nx0; x1 = nx1; a0 = na0; a1 = na1;
     }
     if (act) {
         float *pw = dw_part + (size_t)g * D + lane * 8, *pb = db_part + (size_t)g * D + lane * 8;
-        *reinterpret_cast<float4 *>(pw) = make_float4(dwa[0], dwa[1], dwa[2], dwa[3]);
-        *reinterpret_cast<float4 *>(pw + 4) = make_float4(dwa[4], dwa[5], dwa[6], dwa[7]);
-        *reinterpret_cast<float4 *>(pb) = make_float4(dba[0], dba[1], dba[2], dba[3]);
-        *reinterpret_cast<float4 *>(pb + 4) = make_float4(dba[4], dba[5], dba[6], dba[7]);
+        STORE8(pw, dwa);
+        STORE8(pb, dba);
     }
+}
+
+// The 8-wide kernels apply: D % 8 == 0, D <= 512 and every operand (absent ones are null) on a 16-byte boundary.
+bool ln_wide8(int D, std::initializer_list<const void *> operands)
+{
+    uintptr_t bits = 0;
+    for (const void *p : operands) bits |= (uintptr_t)p;
+    return D % 8 == 0 && D <= 512 && (bits & 15) == 0;
+}
+
+// ln_fwd_vec8_kernel; S > 0: its split-K consumer form.  false: y_dtype is none of the three formats.
+bool launch_fwd_vec8(const float *x, const float *add, int add_rows, float *xs, const float *w, const float *b, void *y, int y_dtype,
+                     float *mean, float *rstd, int M, int D, float eps, const float *sum_bias, const float *parts, int S, void *stream)
+{
+    dim3 vgrid(min((M + 3) / 4, 256 * 8));         // 8 workgroups per CU; each wave walks rows with that stride
+    return ppt_launch3(y_dtype, [&](auto t) {
+        using TY = decltype(t);
+        const auto k = S > 0 ? ln_fwd_vec8_kernel<TY, true> : ln_fwd_vec8_kernel<TY, false>;
+        hipLaunchKernelGGL(k, vgrid, dim3(256), 0, ppt_stream(stream), x, add, add_rows, xs, w, b, (TY *)y, mean, rstd, M, D, eps,
+                           ppt_get_wave_priority(), sum_bias, parts, S);
+    });
+}
+
+// ln_bwd_dx8_kernel; S > 0: dy is S slices
+void launch_bwd_dx8(const float *dy, int S, const float *xs, const float *w, const float *mean, const float *rstd, float *dx,
+                    int accumulate_dx, void *dx_copy, int dx_copy_dtype, int M, int D, void *stream)
+{
+    hipLaunchKernelGGL(ln_bwd_dx8_kernel, dim3((M + 3) / 4), dim3(256), 0, ppt_stream(stream), dy, xs, w, mean, rstd, dx, accumulate_dx,
+                       dx_copy, dx_copy_dtype, M, D, ppt_get_wave_priority(), S);
 }
 
 }  // namespace
@@ -336,33 +351,14 @@ extern "C" int ppt_layernorm_fwd(const float *x, const float *add, int add_rows,
 {
     if (!x || !w || !b || !y || M <= 0 || D <= 0 || D > 64 * MAX_EPL) return PPT_EINVAL;
     if (y_dtype != PPT_BF16 && y_dtype != PPT_F32 && y_dtype != PPT_F16) return PPT_EINVAL;
-    const bool al = (((uintptr_t)x | (uintptr_t)w | (uintptr_t)b | (uintptr_t)y | (uintptr_t)add | (uintptr_t)xs) & 15) == 0;
-    if ((D % 8) == 0 && D <= 512 && al) {
-        dim3 vgrid(min((M + 3) / 4, 256 * 8));         // 8 workgroups per CU; each wave walks rows with that stride
-        if (y_dtype == PPT_BF16)
-            hipLaunchKernelGGL(ln_fwd_vec8_kernel<bf16_t>, vgrid, dim3(256), 0, ppt_stream(stream), x, add, add_rows, xs, w, b,
-                               (bf16_t *)y, mean, rstd, M, D, eps, ppt_get_wave_priority());
-        else if (y_dtype == PPT_F16)
-            hipLaunchKernelGGL(ln_fwd_vec8_kernel<f16_t>, vgrid, dim3(256), 0, ppt_stream(stream), x, add, add_rows, xs, w, b,
-                               (f16_t *)y, mean, rstd, M, D, eps, ppt_get_wave_priority());
-        else
-            hipLaunchKernelGGL(ln_fwd_vec8_kernel<float>, vgrid, dim3(256), 0, ppt_stream(stream), x, add, add_rows, xs, w, b,
-                               (float *)y, mean, rstd, M, D, eps, ppt_get_wave_priority());
-        PPT_CHECK_LAUNCH();
-        return PPT_OK;
-    }
-    dim3 grid((M + 3) / 4);
-    if (y_dtype == PPT_BF16)
-        hipLaunchKernelGGL(ln_fwd_kernel<bf16_t>, grid, dim3(256), 0, ppt_stream(stream), x, add, add_rows, xs, w, b,
-                           (bf16_t *)y, mean, rstd, M, D, eps);
-    else if (y_dtype == PPT_F16)
-        hipLaunchKernelGGL(ln_fwd_kernel<f16_t>, grid, dim3(256), 0, ppt_stream(stream), x, add, add_rows, xs, w, b,
-                           (f16_t *)y, mean, rstd, M, D, eps);
-    else if (y_dtype == PPT_F32)
-        hipLaunchKernelGGL(ln_fwd_kernel<float>, grid, dim3(256), 0, ppt_stream(stream), x, add, add_rows, xs, w, b,
-                           (float *)y, mean, rstd, M, D, eps);
+    if (ln_wide8(D, {x, w, b, y, add, xs}))
+        (void)launch_fwd_vec8(x, add, add_rows, xs, w, b, y, y_dtype, mean, rstd, M, D, eps, nullptr, nullptr, 0, stream);
     else
-        return PPT_EINVAL;
+        (void)ppt_launch3(y_dtype, [&](auto t) {
+            using TY = decltype(t);
+            hipLaunchKernelGGL(ln_fwd_kernel<TY>, dim3((M + 3) / 4), dim3(256), 0, ppt_stream(stream), x, add, add_rows, xs, w, b, (TY *)y,
+                               mean, rstd, M, D, eps);
+        });
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }
@@ -374,9 +370,9 @@ extern "C" int ppt_layernorm_bwd(const float *dy, const float *xs, const float *
     if (!dy || !xs || !w || !mean || !rstd || !dx || M <= 0 || D <= 0 || D > 64 * MAX_EPL) return PPT_EINVAL;
     if ((dw_partial == nullptr) != (db_partial == nullptr)) return PPT_EINVAL;
     if (dw_partial && partial_rows <= 0) return PPT_EINVAL;
-    if (!dw_partial && D % 8 == 0 && D <= 512 && ((((uintptr_t)dy | (uintptr_t)xs | (uintptr_t)w | (uintptr_t)dx | (uintptr_t)dx_copy) & 15) == 0)) {
-        hipLaunchKernelGGL(ln_bwd_dx8_kernel, dim3((M + 3) / 4), dim3(256), 0, ppt_stream(stream), dy, xs, w, mean, rstd, dx, accumulate_dx,
-                           dx_copy, dx_copy_dtype, M, D, ppt_get_wave_priority());
+    const bool wide8 = ln_wide8(D, {dy, xs, w, dx, dx_copy, dw_partial, db_partial});
+    if (!dw_partial && wide8) {
+        launch_bwd_dx8(dy, 0, xs, w, mean, rstd, dx, accumulate_dx, dx_copy, dx_copy_dtype, M, D, stream);
         PPT_CHECK_LAUNCH();
         return PPT_OK;
     }
@@ -389,16 +385,10 @@ extern "C" int ppt_layernorm_bwd(const float *dy, const float *xs, const float *
         (void)hipMemsetAsync(dw_partial + (size_t)used * D, 0, sizeof(float) * (size_t)(partial_rows - used) * D, ppt_stream(stream));
         (void)hipMemsetAsync(db_partial + (size_t)used * D, 0, sizeof(float) * (size_t)(partial_rows - used) * D, ppt_stream(stream));
     }
-    static const bool w8 = getenv("PPT_LN_BWD_W8") == nullptr || atoi(getenv("PPT_LN_BWD_W8")) != 0;
-    if (w8 && dw_partial && D % 8 == 0 && D <= 512 &&
-        ((((uintptr_t)dy | (uintptr_t)xs | (uintptr_t)w | (uintptr_t)dx | (uintptr_t)dx_copy | (uintptr_t)dw_partial | (uintptr_t)db_partial) & 15) == 0)) {
-        hipLaunchKernelGGL(ln_bwd_w8_kernel, dim3((used + 3) / 4), dim3(256), 0, ppt_stream(stream), dy, xs, w, mean, rstd, dx,
-                           accumulate_dx, dx_copy, dx_copy_dtype, dw_partial, db_partial, rpw, M, D, ppt_get_wave_priority());
-        PPT_CHECK_LAUNCH();
-        return PPT_OK;
-    }
-    hipLaunchKernelGGL(ln_bwd_kernel, dim3((used + 3) / 4), dim3(256), 0, ppt_stream(stream), dy, xs, w, mean, rstd, dx,
-                       accumulate_dx, dx_copy, dx_copy_dtype, dw_partial, db_partial, rpw, M, D, ppt_get_wave_priority());
+    // the 16-byte form where it applies (it needs dw / db partials); ln_bwd_kernel for every other shape and alignment
+    const auto k = dw_partial && wide8 ? ln_bwd_w8_kernel : ln_bwd_kernel;
+    hipLaunchKernelGGL(k, dim3((used + 3) / 4), dim3(256), 0, ppt_stream(stream), dy, xs, w, mean, rstd, dx, accumulate_dx, dx_copy,
+                       dx_copy_dtype, dw_partial, db_partial, rpw, M, D, ppt_get_wave_priority());
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }
@@ -410,19 +400,8 @@ extern "C" int ppt_layernorm_fwd_sum(const float *x, const float *bias, const fl
 {
     if (!x || !parts || !xs || !w || !b || !y || S <= 0 || S > 8 || M <= 0 || D <= 0) return PPT_EINVAL;
     if ((D % 8) != 0 || D > 512) return PPT_EUNSUPPORTED;
-    if ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)b | (uintptr_t)y | (uintptr_t)parts | (uintptr_t)xs | (uintptr_t)bias) & 15) != 0) return PPT_EINVAL;
-    dim3 vgrid(min((M + 3) / 4, 256 * 8));
-    if (y_dtype == PPT_BF16)
-        hipLaunchKernelGGL((ln_fwd_vec8_kernel<bf16_t, true>), vgrid, dim3(256), 0, ppt_stream(stream), x, (const float *)nullptr, 0, xs, w, b,
-                           (bf16_t *)y, mean, rstd, M, D, eps, ppt_get_wave_priority(), bias, parts, S);
-    else if (y_dtype == PPT_F16)
-        hipLaunchKernelGGL((ln_fwd_vec8_kernel<f16_t, true>), vgrid, dim3(256), 0, ppt_stream(stream), x, (const float *)nullptr, 0, xs, w, b,
-                           (f16_t *)y, mean, rstd, M, D, eps, ppt_get_wave_priority(), bias, parts, S);
-    else if (y_dtype == PPT_F32)
-        hipLaunchKernelGGL((ln_fwd_vec8_kernel<float, true>), vgrid, dim3(256), 0, ppt_stream(stream), x, (const float *)nullptr, 0, xs, w, b,
-                           (float *)y, mean, rstd, M, D, eps, ppt_get_wave_priority(), bias, parts, S);
-    else
-        return PPT_EINVAL;
+    if (!ln_wide8(D, {x, w, b, y, parts, xs, bias})) return PPT_EINVAL;
+    if (!launch_fwd_vec8(x, nullptr, 0, xs, w, b, y, y_dtype, mean, rstd, M, D, eps, bias, parts, S, stream)) return PPT_EINVAL;
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }
@@ -433,9 +412,8 @@ extern "C" int ppt_layernorm_bwd_sum(const float *dy_parts, int S, const float *
 {
     if (!dy_parts || !xs || !w || !mean || !rstd || !dx || S <= 0 || S > 8 || M <= 0 || D <= 0) return PPT_EINVAL;
     if ((D % 8) != 0 || D > 512) return PPT_EUNSUPPORTED;
-    if ((((uintptr_t)dy_parts | (uintptr_t)xs | (uintptr_t)w | (uintptr_t)dx | (uintptr_t)dx_copy) & 15) != 0) return PPT_EINVAL;
-    hipLaunchKernelGGL(ln_bwd_dx8_kernel, dim3((M + 3) / 4), dim3(256), 0, ppt_stream(stream), dy_parts, xs, w, mean, rstd, dx, accumulate_dx,
-                       dx_copy, dx_copy_dtype, M, D, ppt_get_wave_priority(), S);
+    if (!ln_wide8(D, {dy_parts, xs, w, dx, dx_copy})) return PPT_EINVAL;
+    launch_bwd_dx8(dy_parts, S, xs, w, mean, rstd, dx, accumulate_dx, dx_copy, dx_copy_dtype, M, D, stream);
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }

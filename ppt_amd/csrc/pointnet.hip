@@ -68,6 +68,46 @@ __device__ __forceinline__ void stat_merge(stat3 &a, const stat3 &b)
     a.n = tot;
 }
 
+// Each stripe folds its partials as three fp64 sums -- S1 = sum of sums, S2 = sum of M2, S3 = sum of sum^2 / n --
+// from which (n, mean, M2) of the stripe follow exactly as from a chain of Chan merges (M2 = S2 + S3 - S1^2 / N;
+// fp64 leaves ~1e-16 x N x mean^2 of cancellation error, far below the fp32 inputs), without a division per
+// partial: the walk over the 16 384 x 512 partials of conv3 is then bandwidth-bound (55 -> ~20 us).
+// A macro, expanded in the kernel's scope (as a function -- sums by reference or returned as a struct, the channel bound inside or
+// outside -- both kernels came out with another register allocation): channel c of psum / psq [P, C], partial rows p_first,
+// p_first + p_step, ... below p_end, each of rpp rows except the last (count rows in all); adds to the four doubles named.
+#define BN_FOLD_STRIPE(p_first, p_end, p_step, s1, s2, s3, ntot)                              \
+    do {                                                                                      \
+        const double inv_rpp = 1.0 / (double)rpp;                                             \
+        if (c < C)                                                                            \
+            for (int p = (p_first); p < (p_end); p += (p_step)) {                             \
+                const double n = fmin((double)rpp, count - (double)p * rpp);                  \
+                if (n > 0.0) {                                                                \
+                    const double sv = (double)psum[(size_t)p * C + c];                        \
+                    s1 += sv; s2 += (double)psq[(size_t)p * C + c];                           \
+                    s3 += sv * sv * (n == (double)rpp ? inv_rpp : 1.0 / n);                   \
+                    ntot += n;                                                                \
+                }                                                                             \
+            }                                                                                 \
+    } while (0)
+
+// The end of every fold, for channel c, in two steps; macros over the kernel's own arguments as well (bn_finish_kernel took a
+// function from the fp64 mean and variance unchanged; bn_finalize_kernel came out with another register allocation for that
+// function called after its two branches with a flag or once in each, and for the two steps as functions, __restrict__ or not).
+// 1: the running statistics from the batch's mean and BIASED fp64 variance (the one that normalises, nn.BatchNorm1d).
+#define BN_UPDATE_RUNNING(mean_f, var)                                                    \
+    if (rmean) {                                                                          \
+        const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;        \
+        rmean[c] = (1.0f - momentum) * rmean[c] + momentum * mean_f;                      \
+        rvar[c] = (1.0f - momentum) * rvar[c] + momentum * (float)unbiased;               \
+        if (c == 0 && nbt) *nbt += 1;                                                     \
+    }
+// 2: the affine the next GEMM applies and the moments the backward wants, from the statistics that normalise.
+#define BN_WRITE_AFFINE(mean_f, var_f)                                                                        \
+    const float sc = gamma[c] / sqrtf(var_f + eps);                                                           \
+    scale[c] = sc;                                                                                            \
+    shift[c] = beta[c] - mean_f * sc;                                                                         \
+    if (mean_out) { mean_out[c] = mean_f; rstd_out[c] = 1.0f / sqrtf(var_f + eps); }
+
 __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float *__restrict__ psum, const float *__restrict__ psq,
                                                           int P, double count, int rpp, int C,
                                                           const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -82,22 +122,8 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float *__restri
     const int c = blockIdx.x * CH + tx;
     float mean_f = 0.f, var_f = 1.f;
     if (train) {
-        // Each stripe folds its partials as three fp64 sums -- S1 = sum of sums, S2 = sum of M2, S3 = sum of sum^2 / n --
-        // from which (n, mean, M2) of the stripe follow exactly as from a chain of Chan merges (M2 = S2 + S3 - S1^2 / N;
-        // fp64 leaves ~1e-16 x N x mean^2 of cancellation error, far below the fp32 inputs), without a division per
-        // partial: the walk over the 16 384 x 512 partials of conv3 is then bandwidth-bound (55 -> ~20 us).
         double s1 = 0.0, s2 = 0.0, s3 = 0.0, ntot = 0.0;
-        const double inv_rpp = 1.0 / (double)rpp;
-        if (c < C)
-            for (int p = ty; p < P; p += ST) {
-                const double n = fmin((double)rpp, count - (double)p * rpp);
-                if (n > 0.0) {
-                    const double sv = (double)psum[(size_t)p * C + c];
-                    s1 += sv; s2 += (double)psq[(size_t)p * C + c];
-                    s3 += sv * sv * (n == (double)rpp ? inv_rpp : 1.0 / n);
-                    ntot += n;
-                }
-            }
+        BN_FOLD_STRIPE(ty, P, ST, s1, s2, s3, ntot);
         stat3 acc{0.0, 0.0, 0.0};
         if (ntot > 0.0) acc = stat3{ntot, s1 / ntot, fmax(s2 + s3 - s1 * s1 / ntot, 0.0)};
         red[ty][tx] = acc;
@@ -108,22 +134,14 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float *__restri
         }
         if (ty != 0 || c >= C) return;
         const stat3 t = red[0][tx];
-        const double var = t.m2 / count;                // biased variance normalises (nn.BatchNorm1d)
+        const double var = t.m2 / count;
         mean_f = (float)t.mean; var_f = (float)var;
-        if (rmean) {
-            const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-            rmean[c] = (1.0f - momentum) * rmean[c] + momentum * mean_f;
-            rvar[c] = (1.0f - momentum) * rvar[c] + momentum * (float)unbiased;
-            if (c == 0 && nbt) *nbt += 1;
-        }
+        BN_UPDATE_RUNNING(mean_f, var);
     } else {
         if (ty != 0 || c >= C) return;
         mean_f = rmean[c]; var_f = rvar[c];
     }
-    const float sc = gamma[c] / sqrtf(var_f + eps);
-    scale[c] = sc;
-    shift[c] = beta[c] - mean_f * sc;
-    if (mean_out) { mean_out[c] = mean_f; rstd_out[c] = 1.0f / sqrtf(var_f + eps); }
+    BN_WRITE_AFFINE(mean_f, var_f);
 }
 
 // ---- two-stage fold for many partials (conv3: 16 384 x 512) -----------------------------------------------------
@@ -138,17 +156,7 @@ __global__ __launch_bounds__(1024) void bn_fold_kernel(const float *__restrict__
     const int c = blockIdx.x * 32 + tx;
     const int p0 = blockIdx.y * per_split, p1 = min(P, p0 + per_split);
     double s1 = 0.0, s2 = 0.0, s3 = 0.0, nt = 0.0;
-    const double inv_rpp = 1.0 / (double)rpp;
-    if (c < C)
-        for (int p = p0 + ty; p < p1; p += 32) {
-            const double n = fmin((double)rpp, count - (double)p * rpp);
-            if (n > 0.0) {
-                const double sv = (double)psum[(size_t)p * C + c];
-                s1 += sv; s2 += (double)psq[(size_t)p * C + c];
-                s3 += sv * sv * (n == (double)rpp ? inv_rpp : 1.0 / n);
-                nt += n;
-            }
-        }
+    BN_FOLD_STRIPE(p0 + ty, p1, 32, s1, s2, s3, nt);
     red[0][ty][tx] = s1; red[1][ty][tx] = s2; red[2][ty][tx] = s3; red[3][ty][tx] = nt;
     __syncthreads();
     for (int off = 16; off > 0; off >>= 1) {
@@ -186,18 +194,10 @@ __global__ __launch_bounds__(256) void bn_finish_kernel(const double *__restrict
             if (k0 + u < nsplit) { s1 += a[u][0]; s2 += a[u][1]; s3 += a[u][2]; }
     }
     const double mean = s1 / count;
-    const double var = fmax(s2 + s3 - s1 * s1 / count, 0.0) / count;      // biased variance normalises (nn.BatchNorm1d)
+    const double var = fmax(s2 + s3 - s1 * s1 / count, 0.0) / count;
     const float mean_f = (float)mean, var_f = (float)var;
-    if (rmean) {
-        const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-        rmean[c] = (1.0f - momentum) * rmean[c] + momentum * mean_f;
-        rvar[c] = (1.0f - momentum) * rvar[c] + momentum * (float)unbiased;
-        if (c == 0 && nbt) *nbt += 1;
-    }
-    const float sc = gamma[c] / sqrtf(var_f + eps);
-    scale[c] = sc;
-    shift[c] = beta[c] - mean_f * sc;
-    if (mean_out) { mean_out[c] = mean_f; rstd_out[c] = 1.0f / sqrtf(var_f + eps); }
+    BN_UPDATE_RUNNING(mean_f, var);
+    BN_WRITE_AFFINE(mean_f, var_f);
 }
 
 // ---- BatchNorm over the rows of a row-major [M, C] fp32 tensor (the part-segmentation decoder: BatchNorm1d behind every
@@ -206,6 +206,9 @@ __global__ __launch_bounds__(256) void bn_finish_kernel(const double *__restrict
 // (sum, M2) partial format bn_finalize folds; backward in two kernels: chunk partials of {sum g, sum g xhat} with
 // g = dy * [y > 0] (the fused ReLU), then dx = scale * (g - mean(g) - xhat * mean(g xhat)).
 constexpr int RS_ROWS = 64;
+
+// the gradient behind the fused ReLU: g where the forward's fma(x, scale, shift) was positive, else 0 (NaN: 0)
+__device__ __forceinline__ float relu_masked(float g, float v, float sc, float sh) { return fmaf(v, sc, sh) > 0.f ? g : 0.f; }
 
 __global__ __launch_bounds__(256) void rows_stats_kernel(const float *__restrict__ x, int64_t M, int C,
                                                          float *__restrict__ psum, float *__restrict__ pm2)
@@ -240,7 +243,7 @@ __global__ __launch_bounds__(256) void bn_rows_bwd_reduce_kernel(const float *__
     for (int r = 0; r < nrow; ++r) {
         const float v = x[(r0 + r) * C + c];
         float g = dy[(r0 + r) * C + c];
-        if (relu && !(fmaf(v, sc, sh) > 0.f)) g = 0.f;
+        if (relu) g = relu_masked(g, v, sc, sh);
         sg += g;
         sgx = fmaf(g, (v - mu) * rs, sgx);
     }
@@ -270,7 +273,8 @@ __global__ __launch_bounds__(256) void bn_rows_bwd_reduce_vec_kernel(const float
         for (int r = g; r < nrow; r += 16) {
             const float4 v = *reinterpret_cast<const float4 *>(x + (r0 + r) * C + c);
             float4 gd = *reinterpret_cast<const float4 *>(dy + (r0 + r) * C + c);
-            if (relu) {
+            if (relu) {                                    // relu_masked per component, written out: with the function in any form
+                                                           // (by value, by reference) this kernel got another register allocation
                 if (!(fmaf(v.x, sc.x, sh.x) > 0.f)) gd.x = 0.f;
                 if (!(fmaf(v.y, sc.y, sh.y) > 0.f)) gd.y = 0.f;
                 if (!(fmaf(v.z, sc.z, sh.z) > 0.f)) gd.z = 0.f;
@@ -307,7 +311,7 @@ __global__ __launch_bounds__(256) void bn_rows_bwd_apply_kernel(const float *__r
     for (int r = 0; r < nrow; ++r) {
         const float v = x[(r0 + r) * C + c];
         float g = dy[(r0 + r) * C + c];
-        if (relu && !(fmaf(v, sc, sh) > 0.f)) g = 0.f;
+        if (relu) g = relu_masked(g, v, sc, sh);
         const float o = sc * (g - mg - (v - mu) * rs * mgx);
         if (dx) dx[(r0 + r) * C + c] = o;
         if (dx_half) dx_half[(r0 + r) * C + c] = from_f32_dt(half_dtype, o);
@@ -447,13 +451,10 @@ extern "C" int ppt_bn_act_rows(const float *x, int M, int C, const float *scale,
     if (!x || !scale || !shift || !y || M <= 0 || C <= 0) return PPT_EINVAL;
     const int64_t n = (int64_t)M * C;
     dim3 grid((unsigned)((n + 255) / 256));
-    if (y_dtype == PPT_F32)
-        hipLaunchKernelGGL(bn_act_rows_kernel<float>, grid, dim3(256), 0, ppt_stream(stream), x, n, C, scale, shift, mask, (float *)y);
-    else if (y_dtype == PPT_BF16)
-        hipLaunchKernelGGL(bn_act_rows_kernel<bf16_t>, grid, dim3(256), 0, ppt_stream(stream), x, n, C, scale, shift, mask, (bf16_t *)y);
-    else if (y_dtype == PPT_F16)
-        hipLaunchKernelGGL(bn_act_rows_kernel<f16_t>, grid, dim3(256), 0, ppt_stream(stream), x, n, C, scale, shift, mask, (f16_t *)y);
-    else
+    if (!ppt_launch3(y_dtype, [&](auto t) {
+            using TY = decltype(t);
+            hipLaunchKernelGGL(bn_act_rows_kernel<TY>, grid, dim3(256), 0, ppt_stream(stream), x, n, C, scale, shift, mask, (TY *)y);
+        }))
         return PPT_EINVAL;
     PPT_CHECK_LAUNCH();
     return PPT_OK;
@@ -474,41 +475,14 @@ extern "C" int ppt_conv1_stats(const float *pts, int64_t M, const float *w1, con
     return PPT_OK;
 }
 
-static int bn_finalize_single(const float *part_sum, const float *part_sqsum, int n_partials, int rows_per_partial,
-                              int64_t count, int C,
-                              const float *gamma, const float *beta, float eps, int train, float momentum,
-                              float *running_mean, float *running_var, int64_t *num_batches_tracked, float *scale,
-                              float *shift, float *mean_out, float *rstd_out, void *stream)
-{
-    if (!gamma || !beta || !scale || !shift || C <= 0) return PPT_EINVAL;
-    if ((mean_out == nullptr) != (rstd_out == nullptr)) return PPT_EINVAL;
-    if (train && (!part_sum || !part_sqsum || n_partials <= 0 || count <= 0 || rows_per_partial <= 0 ||
-                  (int64_t)n_partials * rows_per_partial < count))
-        return PPT_EINVAL;
-    if (!train && (!running_mean || !running_var)) return PPT_EINVAL;
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 7) / 8), dim3(1024), 0, ppt_stream(stream), part_sum, part_sqsum,
-                       n_partials, (double)count, rows_per_partial, C, gamma, beta, eps, train, momentum, running_mean, running_var,
-                       num_batches_tracked, scale, shift, mean_out, rstd_out);
-    PPT_CHECK_LAUNCH();
-    return PPT_OK;
-}
-
-extern "C" int ppt_bn_finalize(const float *part_sum, const float *part_sqsum, int n_partials, int rows_per_partial,
-                               int64_t count, int C,
-                               const float *gamma, const float *beta, float eps, int train, float momentum,
-                               float *running_mean, float *running_var, int64_t *num_batches_tracked, float *scale,
-                               float *shift, void *stream)
-{
-    return bn_finalize_single(part_sum, part_sqsum, n_partials, rows_per_partial, count, C, gamma, beta, eps, train, momentum,
-                              running_mean, running_var, num_batches_tracked, scale, shift, nullptr, nullptr, stream);
-}
-
 extern "C" size_t ppt_bn_finalize_workspace_bytes(int n_partials, int C)
 {
     const int nsplit = n_partials >= 2048 ? 32 : 0;          // the single-kernel fold is as fast below that
     return (size_t)nsplit * (size_t)C * 4 * sizeof(double);
 }
 
+// One kernel, or -- training, with the workspace ppt_bn_finalize_workspace_bytes asks for -- the two-stage fold; a workspace that is
+// missing, too small or misaligned silently takes the single kernel.
 extern "C" int ppt_bn_finalize_ws(const float *part_sum, const float *part_sqsum, int n_partials, int rows_per_partial,
                                   int64_t count, int C,
                                   const float *gamma, const float *beta, float eps, int train, float momentum,
@@ -516,14 +490,20 @@ extern "C" int ppt_bn_finalize_ws(const float *part_sum, const float *part_sqsum
                                   float *shift, float *mean_out, float *rstd_out, void *workspace, size_t workspace_bytes,
                                   void *stream)
 {
-    const size_t need = train ? ppt_bn_finalize_workspace_bytes(n_partials, C) : 0;
-    if (need == 0 || !workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))
-        return bn_finalize_single(part_sum, part_sqsum, n_partials, rows_per_partial, count, C, gamma, beta, eps, train, momentum,
-                                  running_mean, running_var, num_batches_tracked, scale, shift, mean_out, rstd_out, stream);
+    if (!gamma || !beta || !scale || !shift || C <= 0) return PPT_EINVAL;
     if ((mean_out == nullptr) != (rstd_out == nullptr)) return PPT_EINVAL;
-    if (!gamma || !beta || !scale || !shift || C <= 0 || !part_sum || !part_sqsum || count <= 0 || rows_per_partial <= 0 ||
-        (int64_t)n_partials * rows_per_partial < count)
+    if (train && (!part_sum || !part_sqsum || n_partials <= 0 || count <= 0 || rows_per_partial <= 0 ||
+                  (int64_t)n_partials * rows_per_partial < count))
         return PPT_EINVAL;
+    if (!train && (!running_mean || !running_var)) return PPT_EINVAL;
+    const size_t need = train ? ppt_bn_finalize_workspace_bytes(n_partials, C) : 0;
+    if (need == 0 || !workspace || workspace_bytes < need || ((uintptr_t)workspace & 7)) {
+        hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 7) / 8), dim3(1024), 0, ppt_stream(stream), part_sum, part_sqsum,
+                           n_partials, (double)count, rows_per_partial, C, gamma, beta, eps, train, momentum, running_mean, running_var,
+                           num_batches_tracked, scale, shift, mean_out, rstd_out);
+        PPT_CHECK_LAUNCH();
+        return PPT_OK;
+    }
     const int nsplit = 32, per_split = (n_partials + nsplit - 1) / nsplit;
     hipLaunchKernelGGL(bn_fold_kernel, dim3((C + 31) / 32, nsplit), dim3(1024), 0, ppt_stream(stream), part_sum, part_sqsum,
                        n_partials, (double)count, rows_per_partial, C, per_split, (double *)workspace);
@@ -535,12 +515,30 @@ extern "C" int ppt_bn_finalize_ws(const float *part_sum, const float *part_sqsum
     return PPT_OK;
 }
 
+extern "C" int ppt_bn_finalize(const float *part_sum, const float *part_sqsum, int n_partials, int rows_per_partial,
+                               int64_t count, int C,
+                               const float *gamma, const float *beta, float eps, int train, float momentum,
+                               float *running_mean, float *running_var, int64_t *num_batches_tracked, float *scale,
+                               float *shift, void *stream)
+{
+    return ppt_bn_finalize_ws(part_sum, part_sqsum, n_partials, rows_per_partial, count, C, gamma, beta, eps, train, momentum,
+                              running_mean, running_var, num_batches_tracked, scale, shift, nullptr, nullptr, nullptr, 0, stream);
+}
+
 extern "C" int ppt_rows_stats_rows_per_partial(void) { return RS_ROWS; }
+
+// Row chunks of RS_ROWS = grid.y of the rows kernels; 0 for no rows and for more chunks than the 65 535 a grid takes.
+static unsigned rs_chunks(int64_t M)
+{
+    const int64_t n = (M + RS_ROWS - 1) / RS_ROWS;
+    return M <= 0 || n > 65535 ? 0u : (unsigned)n;
+}
 
 extern "C" int ppt_rows_stats_f32(const float *x, int64_t M, int C, float *part_sum, float *part_m2, void *stream)
 {
-    if (!x || !part_sum || !part_m2 || M <= 0 || C <= 0 || (M + RS_ROWS - 1) / RS_ROWS > 65535) return PPT_EINVAL;
-    hipLaunchKernelGGL(rows_stats_kernel, dim3((C + 255) / 256, (unsigned)((M + RS_ROWS - 1) / RS_ROWS)), dim3(256), 0,
+    const unsigned chunks = rs_chunks(M);
+    if (!x || !part_sum || !part_m2 || !chunks || C <= 0) return PPT_EINVAL;
+    hipLaunchKernelGGL(rows_stats_kernel, dim3((C + 255) / 256, chunks), dim3(256), 0,
                        ppt_stream(stream), x, M, C, part_sum, part_m2);
     PPT_CHECK_LAUNCH();
     return PPT_OK;
@@ -550,15 +548,14 @@ extern "C" int ppt_bn_rows_bwd_reduce(const float *dy, const float *x, const flo
                                       const float *mean, const float *rstd, int relu, int64_t M, int C, float *part_g,
                                       float *part_gx, void *stream)
 {
-    if (!dy || !x || !scale || !shift || !mean || !rstd || !part_g || !part_gx || M <= 0 || C <= 0 ||
-        (M + RS_ROWS - 1) / RS_ROWS > 65535)
-        return PPT_EINVAL;
+    const unsigned chunks = rs_chunks(M);
+    if (!dy || !x || !scale || !shift || !mean || !rstd || !part_g || !part_gx || !chunks || C <= 0) return PPT_EINVAL;
     if (C % 4 == 0 && !(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)mean | (uintptr_t)rstd |
                           (uintptr_t)part_g | (uintptr_t)part_gx) & 15))
-        hipLaunchKernelGGL(bn_rows_bwd_reduce_vec_kernel, dim3((C + 63) / 64, (unsigned)((M + RS_ROWS - 1) / RS_ROWS)), dim3(256), 0,
+        hipLaunchKernelGGL(bn_rows_bwd_reduce_vec_kernel, dim3((C + 63) / 64, chunks), dim3(256), 0,
                            ppt_stream(stream), dy, x, scale, shift, mean, rstd, relu, M, C, part_g, part_gx);
     else
-        hipLaunchKernelGGL(bn_rows_bwd_reduce_kernel, dim3((C + 255) / 256, (unsigned)((M + RS_ROWS - 1) / RS_ROWS)), dim3(256), 0,
+        hipLaunchKernelGGL(bn_rows_bwd_reduce_kernel, dim3((C + 255) / 256, chunks), dim3(256), 0,
                            ppt_stream(stream), dy, x, scale, shift, mean, rstd, relu, M, C, part_g, part_gx);
     PPT_CHECK_LAUNCH();
     return PPT_OK;
@@ -568,11 +565,11 @@ extern "C" int ppt_bn_rows_bwd_apply(const float *dy, const float *x, const floa
                                      const float *rstd, const float *sum_g, const float *sum_gx, int relu, int batch_stats,
                                      int64_t M, int C, float *dx, void *dx_half, int half_dtype, void *stream)
 {
-    if (!dy || !x || !scale || !shift || !mean || !rstd || (!dx && !dx_half) || M <= 0 || C <= 0 || (M + RS_ROWS - 1) / RS_ROWS > 65535)
-        return PPT_EINVAL;
+    const unsigned chunks = rs_chunks(M);
+    if (!dy || !x || !scale || !shift || !mean || !rstd || (!dx && !dx_half) || !chunks || C <= 0) return PPT_EINVAL;
     if (dx_half && half_dtype != PPT_BF16 && half_dtype != PPT_F16) return PPT_EINVAL;
     if (batch_stats && (!sum_g || !sum_gx)) return PPT_EINVAL;
-    hipLaunchKernelGGL(bn_rows_bwd_apply_kernel, dim3((C + 255) / 256, (unsigned)((M + RS_ROWS - 1) / RS_ROWS)), dim3(256), 0,
+    hipLaunchKernelGGL(bn_rows_bwd_apply_kernel, dim3((C + 255) / 256, chunks), dim3(256), 0,
                        ppt_stream(stream), dy, x, scale, shift, mean, rstd, sum_g, sum_gx, relu, batch_stats, M, C, dx,
                        (uint16_t *)dx_half, half_dtype);
     PPT_CHECK_LAUNCH();
@@ -585,13 +582,10 @@ extern "C" int ppt_linear3_gelu(const float *pts, int64_t M, const float *w, con
     if (!pts || !w || !b || !y || M <= 0 || C <= 0) return PPT_EINVAL;
     const int64_t n = M * C;
     dim3 grid((unsigned)((n + 255) / 256));
-    if (y_dtype == PPT_BF16)
-        hipLaunchKernelGGL(linear3_gelu_kernel<bf16_t>, grid, dim3(256), 0, ppt_stream(stream), pts, M, w, b, C, (bf16_t *)y);
-    else if (y_dtype == PPT_F16)
-        hipLaunchKernelGGL(linear3_gelu_kernel<f16_t>, grid, dim3(256), 0, ppt_stream(stream), pts, M, w, b, C, (f16_t *)y);
-    else if (y_dtype == PPT_F32)
-        hipLaunchKernelGGL(linear3_gelu_kernel<float>, grid, dim3(256), 0, ppt_stream(stream), pts, M, w, b, C, (float *)y);
-    else
+    if (!ppt_launch3(y_dtype, [&](auto t) {
+            using TY = decltype(t);
+            hipLaunchKernelGGL(linear3_gelu_kernel<TY>, grid, dim3(256), 0, ppt_stream(stream), pts, M, w, b, C, (TY *)y);
+        }))
         return PPT_EINVAL;
     PPT_CHECK_LAUNCH();
     return PPT_OK;

@@ -322,3 +322,16 @@ template <typename Fn> static inline void ppt_launch16(int dtype, Fn &&fn)
 {
     if (dtype == PPT_F16) fn(f16_t{}); else fn(bf16_t{});
 }
+
+// The three-format launch: fn(T{}) with T = float, bf16_t or f16_t for dtype = PPT_F32 / PPT_BF16 / PPT_F16; any other code calls
+// nothing and returns false, and the caller returns ITS error for an unsupported format (PPT_EINVAL or PPT_EUNSUPPORTED):
+//     if (!ppt_launch3(dtype, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL(kernel<T>, ..., (T *)y); })) return PPT_EINVAL;
+// Nested, it spells a source x destination table (ppt_convert_scaled, ppt_transpose).
+template <typename Fn> static inline bool ppt_launch3(int dtype, Fn &&fn)
+{
+    if (dtype == PPT_F32) fn(float{});
+    else if (dtype == PPT_BF16) fn(bf16_t{});
+    else if (dtype == PPT_F16) fn(f16_t{});
+    else return false;
+    return true;
+}

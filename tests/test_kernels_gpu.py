@@ -582,9 +582,10 @@ def test_bn_finalize_many_partials(ops, P, C, rpp, tail):
     assert torch.equal(sc_b, sc) and torch.equal(sh_b, sh)
 
 
-@pytest.mark.parametrize("M,C,training", [(1000, 96, True), (4096, 384, True), (130, 40, False)])
+@pytest.mark.parametrize("M,C,training", [(1000, 96, True), (4096, 384, True), (130, 40, False), (66, 30, True)])
 def test_batch_norm_relu_rows_matches_torch(ops, M, C, training):
-    """relu(BatchNorm1d(x)) over rows with trainable gamma / beta: forward, running statistics, dx, d gamma, d beta."""
+    """relu(BatchNorm1d(x)) over rows with trainable gamma / beta: forward, running statistics, dx, d gamma, d beta.
+    (66, 30): C % 4 != 0 takes the one-thread-per-column backward reduction, 66 rows leave a ragged second chunk of 64."""
     from ppt_amd.autograd import batch_norm_relu_rows
     torch.manual_seed(M + C)
     x = (torch.randn(M, C) * 2 + torch.randn(C) * 3).cuda().requires_grad_(True)
@@ -641,10 +642,33 @@ def test_misc_ops(ops):
     ref = torch.cat([xt[:, 0], xt[:, 1:].max(1)[0]], -1)
     assert torch.equal(out.cpu(), ref)
     assert torch.equal(am.cpu().long(), xt[:, 1:].max(1)[1] + 1)
+    for half in (torch.bfloat16, torch.float16):                # 16-bit inputs: exact on the rounded values
+        xh = xt.to(half)
+        out, am = ops.cls_max_pool(xh.cuda(), want_argmax=True)
+        assert torch.equal(out.cpu(), torch.cat([xh[:, 0], xh[:, 1:].max(1)[0]], -1).float())
+        assert torch.equal(am.cpu().long(), xh[:, 1:].max(1)[1] + 1)
     a = rng.standard_normal((130, 70)).astype(np.float32)
     t = ops.transpose(dev(a), torch.bfloat16)
     assert torch.equal(t.cpu(), torch.from_numpy(a).t().contiguous().to(torch.bfloat16))
     assert torch.equal(ops.convert(dev(a), torch.bfloat16).cpu(), torch.from_numpy(a).to(torch.bfloat16))
+    # every (source, destination) pair of the three formats; 64 x 64: fp32 -> 16 bit takes the eight-per-thread kernel.
+    # ops.convert returns its input for equal formats, so the copy goes through ppt_convert itself.
+    from ppt_amd import _lib
+
+    def convert(src, dst_dtype):
+        dst = torch.empty(src.shape, dtype=dst_dtype, device=src.device)
+        _lib.check(_lib.lib().ppt_convert(ops._p(src), ops.dtype_code(src), ops._p(dst), ops.dtype_code(dst), src.numel(),
+                                          ops._stream()), "ppt_convert")
+        return dst
+
+    formats = (torch.float32, torch.bfloat16, torch.float16)
+    a64 = rng.standard_normal((64, 64)).astype(np.float32)
+    for sd in formats:
+        s, s64 = torch.from_numpy(a).to(sd), torch.from_numpy(a64).to(sd)
+        for dd in formats:
+            assert torch.equal(ops.transpose(s.cuda(), dd).cpu(), s.t().contiguous().to(dd)), (sd, dd)
+            assert torch.equal(convert(s.cuda(), dd).cpu(), s.to(dd)), (sd, dd)
+            assert torch.equal(convert(s64.cuda(), dd).cpu(), s64.to(dd)), (sd, dd)
     pts = rng.standard_normal((1000, 3)).astype(np.float32)
     w = rng.standard_normal((128, 3)).astype(np.float32)
     b = rng.standard_normal(128).astype(np.float32)
