@@ -49,7 +49,8 @@ const char *ppt_strerror(int code);
  *    ppt_text_lin_retile_split (csrc/text_lin.hip); later, additive only (no existing signature or struct changed):
  *    ppt_text_lin16 / ppt_text_lin_retile16 (the 16-bit form of ppt_text_lin_split); ppt_cloud_prep_f32 / ppt_cloud_draws (csrc/cloud_prep.hip);
  *    ppt_cls_metrics / ppt_partseg_metrics / ppt_partseg_metrics_chunks (csrc/metrics.hip);
- *    ppt_logreg_fit_f32 / ppt_logreg_predict_f32 / ppt_logreg_workspace_bytes (csrc/logreg.hip).
+ *    ppt_logreg_fit_f32 / ppt_logreg_predict_f32 / ppt_logreg_workspace_bytes (csrc/logreg.hip);
+ *    ppt_nearest_rows_f32 / ppt_nearest_rows_workspace_bytes (csrc/nearest.hip).
  * 6: ppt_gemm_params.split16 / split_a_pow2 / split_b_pow2 (new trailing fields: fp32 operands as hi + lo half pairs),
  *    ppt_attention_fwd_split16 / ppt_attention_bwd_split16 (new), ppt_pointmlp_cloud_rstd / ppt_pointmlp_pq (new).
  * 5: ppt_labels_check (new), ppt_gemm256 (new: the 256-row macro-tile GEMM core), ppt_set_gemm256 / ppt_get_gemm256 (new),
@@ -836,6 +837,22 @@ int ppt_logreg_fit_f32(const float *feat, int64_t ld, int Nbank, const int64_t *
                        size_t workspace_bytes, void *stream);
 int ppt_logreg_predict_f32(const float *feat, int64_t ld, int Nbank, const int32_t *rows, int n_eval, const float *W,
                            const float *b, int F, int d, int K, int32_t *pred, void *stream);
+
+/* ---- nearest table rows (ABI 7, additive; csrc/nearest.hip; host side: ppt_amd/analysis.py) -------------------------------------
+ * What interpret_prompt.py:34-37 asks of torch.cdist + argsort: for each of the Q query rows the k table rows at the smallest
+ * Euclidean distance, in ascending order, equal distances in ascending row order.
+ *   q [Q, D] f32 contiguous; table [V, ld >= D] f32 with unit column stride, 16-byte aligned, ld % 4 == 0;
+ *   idx [Q, k] int32; dist [Q, k] f32.
+ * The distance is the direct form sqrt(sum_j (q_j - t_j)^2) accumulated in fp32 over the columns in order (not cdist's expanded
+ * form): a query that is a copy of a table row is at distance exactly 0 from it.  The order is that of the 64-bit keys
+ * (bits of d^2) << 32 | row; a row at a distance that is not finite never precedes a finite one.  Two passes, no atomics, the same
+ * bytes on every run: one workgroup per 256 table rows writes the k best keys of each half of them per query to the workspace, one
+ * workgroup per query merges these lists.  The table is read once (once per 32 queries); no [Q, V] matrix is written.
+ *   workspace: ppt_nearest_rows_workspace_bytes(Q, V, D, k) bytes, 256-byte aligned (0 for an unsupported shape).
+ *   1 <= Q, Q * D <= 32768, D % 4 == 0, 1 <= k <= min(V, 64): PPT_EUNSUPPORTED outside (nothing launched). */
+size_t ppt_nearest_rows_workspace_bytes(int Q, int V, int D, int k);
+int ppt_nearest_rows_f32(const float *q, int Q, const float *table, int64_t ld, int V, int D, int k, int32_t *idx, float *dist,
+                         void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -250,6 +250,9 @@ _SIGNATURES = {
                                    c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
     "ppt_logreg_predict_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                        c_void_p]),
+    "ppt_nearest_rows_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
+    "ppt_nearest_rows_f32": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                     ctypes.c_size_t, c_void_p]),
 }
 
 

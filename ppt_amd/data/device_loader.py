@@ -150,6 +150,22 @@ class DeviceCloudSet:
     def __len__(self):
         return self.points.shape[0]
 
+    def subset(self, indices):
+        """A new DeviceCloudSet over the clouds `indices` (host integers, e.g. data.fewshot.fewshot_indices; repeats allowed), in
+        that order: index_select on the device, `seg` and `lengths` follow, no cloud travels through the host."""
+        idx = np.asarray(indices.cpu() if torch.is_tensor(indices) else indices).reshape(-1).astype(np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= len(self)):
+            raise IndexError(f"DeviceCloudSet.subset: indices outside [0, {len(self)})")
+        item = torch.from_numpy(idx).to(self.device)
+        new = object.__new__(DeviceCloudSet)
+        new.device = self.device
+        new.lengths_host = None if self.lengths_host is None else self.lengths_host[idx]
+        new.points = self.points.index_select(0, item)
+        new.labels = self.labels.index_select(0, item)
+        new.seg = None if self.seg is None else self.seg.index_select(0, item)
+        new.lengths = None if self.lengths is None else self.lengths.index_select(0, item)
+        return new
+
     def rows(self, idx):
         """valid rows of the clouds `idx` (host array)"""
         if self.lengths_host is None:
@@ -241,6 +257,8 @@ class DeviceBatchLoader:
         part = self.recipe == "shapenetpart"
         if self.draws == "numpy":
             d = self._host_draws(rs, idx)
+        elif not (self._fps_rows > 0 or self.train or part):
+            d = {}                        # a test split that takes the stored rows as they are: nothing is drawn
         else:
             rows = None if s.lengths is None else s.lengths.index_select(0, item)
             d = ops.cloud_draws(item, n, self.seed, self.epoch, rows=rows, rows_all=s.points.shape[1], start=self._fps_rows > 0,

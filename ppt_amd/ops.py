@@ -1333,6 +1333,32 @@ def logreg_predict(feat, W, b, rows=None):
     return pred
 
 
+def nearest_rows(q, table, k, workspace=None):
+    """For each row of q [Q, D] f32 the k rows of table [V, >= D] f32 (padded rows allowed) at the smallest Euclidean distance,
+    ascending, ties to the lower row (ppt_nearest_rows_f32: the direct form sqrt(sum (q - t)^2) in fp32).
+    -> (idx [Q, k] int32, dist [Q, k] f32).  workspace: a caller-owned uint8 tensor of at least
+    nearest_rows_workspace_bytes(Q, V, D, k) bytes (allocated when None)."""
+    _chk(q, torch.float32, "q")
+    if q.dim() != 2:
+        raise RuntimeError("nearest_rows: q must be [Q, D]")
+    Q, D = q.shape
+    ld, V = _bank(table, D)
+    k = int(k)
+    need = _lib.lib().ppt_nearest_rows_workspace_bytes(Q, V, D, k)
+    if workspace is None:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=q.device)
+    idx = torch.empty((Q, k), dtype=torch.int32, device=q.device)
+    dist = torch.empty((Q, k), dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().ppt_nearest_rows_f32(_p(q), Q, _p(table), ld, V, D, k, _p(idx), _p(dist), _p(workspace), workspace.numel(),
+                                               _stream()), "ppt_nearest_rows_f32")
+    return idx, dist
+
+
+def nearest_rows_workspace_bytes(Q, V, D, k):
+    """bytes of scratch ppt_nearest_rows_f32 needs for Q queries, V table rows of D columns and k results (0: unsupported shape)"""
+    return _lib.lib().ppt_nearest_rows_workspace_bytes(int(Q), int(V), int(D), int(k))
+
+
 def health_check(x, flags, bit, maxabs=None):
     """flags[0] |= bit if x (any dtype, contiguous) holds a non-finite value; maxabs[0] = max(maxabs[0], max |finite x|) when
     given (ppt_health_check).  flags: int32 [1]; maxabs: f32 [1], non-negative."""
