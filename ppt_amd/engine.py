@@ -12,6 +12,7 @@ all gradients that are accumulated stay fp32 in both modes.
 
 Reference citations are relative to the upstream repo.
 """
+import collections
 import os
 
 import torch
@@ -251,6 +252,39 @@ def _mlp_weights(sd, p, wc):
     return wc.derived(("vit_mlp_tiled", p, ops.VIT_MLP_VARIANT), (w1, w2), lambda: ops.vit_mlp_retile(wc.get(w1), wc.get(w2)))
 
 
+_VitBlockPlan = collections.namedtuple("_VitBlockPlan", "qkv proj mlp")
+
+
+def _vit_block_plan(rows, D, hidden, qkv_out, T, keep, pos_in_x, contiguous):
+    """Which kernel each linear stage of a ViT block runs on (vit_block_forward); reads the switches when called.
+      qkv:  "ln_gemm" | "ln_rowgemm": a LayerNorm launch + ppt_gemm | rowgemm; "rowgemm_ln": the LayerNorm in rowgemm's prologue; "lnlin"
+      proj: "gemm" | "rowgemm" | "fused": attn.proj + DropPath + residual ride in front of the MLP kernel (csrc/mlp_fused.hip, round 3)
+      mlp:  "gemm": LayerNorm, fc1, fc2 as three launches | "rowgemm": norm2 in fc1's prologue, fc2 on ppt_gemm |
+            "fused": LayerNorm + fc1 + GELU + fc2 + DropPath + residual (+ the next block's "+ pos") in one kernel
+    A frozen block (nothing kept) on 16-bit operands from ROWGEMM_MIN_ROWS token rows on: every linear takes what BLOCK_PATH says
+    (round 5; its "v2" is ppt_gemm, which routes these row counts to the 256-row macro-tile core, csrc/gemm256.hip); the first block's
+    LayerNorm has to form x + pos, so its qkv keeps the LayerNorm launch.  Every other block: ppt_gemm, the fused MLP where it
+    exists, and attn.proj in front of it from 8 192 rows (~100 chunks of 80 rows) on: with few rows the MLP kernel runs on a handful
+    of CUs and the proj GEMM is better off as a launch of its own over all of them (C5, 2 064 rows: 6.39 ms separate, 6.44 fused).
+    The sums of the residual stream are formed in the same order on every path."""
+    half = T in ops.HALF
+    fusable = FUSED_MLP and half and not keep and D == 384 and hidden == 1536 and contiguous
+    if not (rows >= ROWGEMM_MIN_ROWS and half and not keep and D in ops.ROWGEMM_K):
+        return _VitBlockPlan("ln_gemm", "fused" if fusable and FUSED_PROJ and rows >= 8192 else "gemm", "fused" if fusable else "gemm")
+    qkv, proj, mlp = BLOCK_PATH["qkv"], BLOCK_PATH["proj"], BLOCK_PATH["mlp"]
+    if qkv == "auto":
+        qkv = "lnlin" if rows <= LNLIN_MAX_ROWS else "rowgemm"
+    if qkv not in ("lnlin", "rowgemm"):
+        qkv = "ln_gemm"
+    elif not pos_in_x:
+        qkv = "ln_rowgemm"
+    elif qkv == "rowgemm" or qkv_out % 384:
+        qkv = "rowgemm_ln"
+    mlp = "gemm" if mlp == "v2" else "fused" if mlp == "fused" and fusable else "rowgemm"
+    proj = "gemm" if proj == "v2" else "fused" if proj == "fused" and mlp == "fused" and FUSED_PROJ else "rowgemm"
+    return _VitBlockPlan(qkv, proj, mlp)
+
+
 def vit_block_forward(sd, p, wc, x, pos, B, Tn, heads, dp1, dp2, save=None, pos_in_x=False, add_pos_out=False):
     """Block.forward on block(x + pos) (point_encoder.py:76-79,103).  x [B*Tn, D] fp32 is updated in
     place unless `save` (a dict) is given: then every intermediate the backward needs is kept.
@@ -258,104 +292,56 @@ def vit_block_forward(sd, p, wc, x, pos, B, Tn, heads, dp1, dp2, save=None, pos_
     neither reads pos nor rewrites the residual stream; the sums are formed in the same order either way."""
     T = wc.dtype
     keep = save is not None
-    if x.shape[0] >= ROWGEMM_MIN_ROWS and T in ops.HALF and not keep and x.shape[1] in ops.ROWGEMM_K:
-        # frozen block, nothing kept: every linear picks its kernel (BLOCK_PATH; round 5) --
-        #   "rowgemm": csrc/rowgemm.hip, the K = 384 weight stationary in registers, the LayerNorm applied while the rows are staged;
-        #   "v2": a LayerNorm launch + ppt_gemm, which routes these row counts to the 256-row macro-tile core (csrc/gemm256.hip);
-        #   "fused" (proj / mlp): attn.proj in front of / the whole MLP branch inside csrc/mlp_fused.hip.
-        # The residual stream is updated in place; the sums are formed in the same order on every path.
-        path = BLOCK_PATH
-        if path["qkv"] == "auto":
-            path = dict(path, qkv="lnlin" if x.shape[0] <= LNLIN_MAX_ROWS else "rowgemm")
-        fused_ok = FUSED_MLP and sd[p + "mlp.fc1.weight"].shape[0] == 1536
-        mlp = path["mlp"] if (fused_ok or path["mlp"] != "fused") else "rowgemm"
-        proj = path["proj"] if not (path["proj"] == "fused" and not (mlp == "fused" and FUSED_PROJ)) else "rowgemm"
-        if pos_in_x and path["qkv"] == "lnlin" and sd[p + "attn.qkv.weight"].shape[0] % 384 == 0:
-            # csrc/lnlin.hip (round 6): rows stationary, weight streamed in fragment order, two workgroups per CU
-            wq = sd[p + "attn.qkv.weight"]
-            wqt = wc.derived(("lnlin_tiled", p), (wq,), lambda: ops.lnlin_retile(wc.get(wq)))
-            qkv = ops.lnlin(x, wqt, (sd[p + "norm1.weight"], sd[p + "norm1.bias"]))
-        elif pos_in_x and path["qkv"] in ("rowgemm", "lnlin"):
-            qkv = ops.rowgemm(x, wc.get(sd[p + "attn.qkv.weight"]), ln=(sd[p + "norm1.weight"], sd[p + "norm1.bias"]))
-        else:           # (the first block: x + pos is formed -- and written back -- by the LayerNorm kernel)
-            if pos_in_x:
-                h, _, _ = ops.layernorm_fwd(x, sd[p + "norm1.weight"], sd[p + "norm1.bias"], T)
-            else:
-                h, _, _ = ops.layernorm_fwd(x, sd[p + "norm1.weight"], sd[p + "norm1.bias"], T, add=pos, write_xs=x)
-            if path["qkv"] in ("rowgemm", "lnlin"):
-                qkv = ops.rowgemm(h, wc.get(sd[p + "attn.qkv.weight"]))
-            else:
-                qkv = ops.gemm(h, wc.get(sd[p + "attn.qkv.weight"]), out_dtype=T)
-        a, _ = ops.attention_fwd(qkv, B, Tn, heads, ATTN_SCALE, False, want_lse=False)
-        if proj == "fused":
-            # attn.proj + DropPath + residual ride in front of the MLP kernel (csrc/mlp_fused.hip, round 3)
-            w1t, w2t = _mlp_weights(sd, p, wc)
+    plan = _vit_block_plan(x.shape[0], x.shape[1], sd[p + "mlp.fc1.weight"].shape[0], sd[p + "attn.qkv.weight"].shape[0], T, keep,
+                           pos_in_x, x.is_contiguous())
+
+    def stream():            # where the residual stream goes next: a fresh tensor when keeping, x itself (in place) otherwise
+        return torch.empty_like(x) if keep else x
+    ln1, ln2 = (sd[p + "norm1.weight"], sd[p + "norm1.bias"]), (sd[p + "norm2.weight"], sd[p + "norm2.bias"])
+    res2 = pos if add_pos_out else None
+    # norm1 + qkv
+    xs, h, mean1, rstd1 = x, None, None, None
+    if plan.qkv == "lnlin":
+        wq = sd[p + "attn.qkv.weight"]
+        qkv = ops.lnlin(x, wc.derived(("lnlin_tiled", p), (wq,), lambda: ops.lnlin_retile(wc.get(wq))), ln1)
+    elif plan.qkv == "rowgemm_ln":
+        qkv = ops.rowgemm(x, wc.get(sd[p + "attn.qkv.weight"]), ln=ln1)
+    else:
+        if not pos_in_x:    # (the first block: x + pos is formed -- and written to the stream -- by the LayerNorm kernel)
+            xs = stream()
+        h, mean1, rstd1 = ops.layernorm_fwd(x, *ln1, T, add=None if pos_in_x else pos, write_xs=None if pos_in_x else xs, save_stats=keep)
+        wq = wc.get(sd[p + "attn.qkv.weight"])
+        qkv = ops.rowgemm(h, wq) if plan.qkv == "ln_rowgemm" else ops.gemm(h, wq, out_dtype=T)
+    a, lse = ops.attention_fwd(qkv, B, Tn, heads, ATTN_SCALE, False, want_lse=keep)
+    # attn.proj + DropPath + residual ("fused": inside the MLP kernel below)
+    x_mid = stream()
+    if plan.proj == "rowgemm":
+        ops.rowgemm(a, wc.get(sd[p + "attn.proj.weight"]), bias=sd[p + "attn.proj.bias"], residual=xs, out=x_mid, row_scale=dp1,
+                    row_scale_rows=Tn)
+    elif plan.proj == "gemm":
+        ops.gemm(a, wc.get(sd[p + "attn.proj.weight"]), out=x_mid, bias=sd[p + "attn.proj.bias"], row_scale=dp1, row_scale_rows=Tn,
+                 residual=xs)
+    # norm2 + fc1 + GELU + fc2 + DropPath + residual (+ the next block's "+ pos")
+    if plan.mlp == "fused":             # (nothing is kept on this path)
+        w1t, w2t = _mlp_weights(sd, p, wc)
+        tail = None
+        if plan.proj == "fused":
             wp = sd[p + "attn.proj.weight"]
             wpt = wc.derived(("vit_proj_tiled", p), (wp,), lambda: ops.vit_proj_retile(wc.get(wp)))
-            ops.vit_mlp(x, w1t, sd[p + "mlp.fc1.bias"], w2t, sd[p + "mlp.fc2.bias"],
-                        (sd[p + "norm2.weight"], sd[p + "norm2.bias"]), row_scale=dp2, row_scale_rows=Tn,
-                        residual2=pos if add_pos_out else None, proj=(a, wpt, sd[p + "attn.proj.bias"], dp1, Tn))
-            return x
-        if proj == "v2":
-            ops.gemm(a, wc.get(sd[p + "attn.proj.weight"]), out=x, bias=sd[p + "attn.proj.bias"], row_scale=dp1, row_scale_rows=Tn,
-                     residual=x)
-        else:
-            ops.rowgemm(a, wc.get(sd[p + "attn.proj.weight"]), bias=sd[p + "attn.proj.bias"], residual=x, out=x, row_scale=dp1,
-                        row_scale_rows=Tn)
-        if mlp == "fused":
-            w1t, w2t = _mlp_weights(sd, p, wc)
-            ops.vit_mlp(x, w1t, sd[p + "mlp.fc1.bias"], w2t, sd[p + "mlp.fc2.bias"],
-                        (sd[p + "norm2.weight"], sd[p + "norm2.bias"]), row_scale=dp2, row_scale_rows=Tn,
-                        residual2=pos if add_pos_out else None)
-            return x
-        if mlp == "v2":
-            h2, _, _ = ops.layernorm_fwd(x, sd[p + "norm2.weight"], sd[p + "norm2.bias"], T)
-            f = ops.gemm(h2, wc.get(sd[p + "mlp.fc1.weight"]), out_dtype=T, bias=sd[p + "mlp.fc1.bias"], act=ACT_GELU)
-        else:
-            f = ops.rowgemm(x, wc.get(sd[p + "mlp.fc1.weight"]), ln=(sd[p + "norm2.weight"], sd[p + "norm2.bias"]),
-                            bias=sd[p + "mlp.fc1.bias"], act=ACT_GELU)
-        ops.gemm(f, wc.get(sd[p + "mlp.fc2.weight"]), out=x, bias=sd[p + "mlp.fc2.bias"], row_scale=dp2, row_scale_rows=Tn,
-                 residual=x, residual2=pos if add_pos_out else None)
-        return x
-    T = wc.dtype
-    keep = save is not None
-    if pos_in_x:
-        xs = x
-        h, mean1, rstd1 = ops.layernorm_fwd(x, sd[p + "norm1.weight"], sd[p + "norm1.bias"], T, save_stats=keep)
+            tail = (a, wpt, sd[p + "attn.proj.bias"], dp1, Tn)
+        return ops.vit_mlp(x_mid, w1t, sd[p + "mlp.fc1.bias"], w2t, sd[p + "mlp.fc2.bias"], ln2, row_scale=dp2, row_scale_rows=Tn,
+                           residual2=res2, proj=tail)
+    h2 = mean2 = rstd2 = pre = None
+    if plan.mlp == "rowgemm":
+        f = ops.rowgemm(x_mid, wc.get(sd[p + "mlp.fc1.weight"]), ln=ln2, bias=sd[p + "mlp.fc1.bias"], act=ACT_GELU)
     else:
-        xs = torch.empty_like(x) if keep else x
-        h, mean1, rstd1 = ops.layernorm_fwd(x, sd[p + "norm1.weight"], sd[p + "norm1.bias"], T, add=pos, write_xs=xs,
-                                            save_stats=keep)
-    qkv = ops.gemm(h, wc.get(sd[p + "attn.qkv.weight"]), out_dtype=T)
-    a, lse = ops.attention_fwd(qkv, B, Tn, heads, ATTN_SCALE, False, want_lse=keep)
-    x_mid = torch.empty_like(x) if keep else xs
-    fused_mlp = (FUSED_MLP and not keep and T in ops.HALF and x.shape[1] == 384 and sd[p + "mlp.fc1.weight"].shape[0] == 1536
-                 and x_mid.is_contiguous())
-    if fused_mlp and FUSED_PROJ and a.is_contiguous() and x.shape[0] >= 8192:
-        # frozen block: attn.proj + DropPath + residual in front of the fused MLP kernel (csrc/mlp_fused.hip, round 3).  From
-        # ~100 chunks of 80 rows on: with few rows the MLP kernel runs on a handful of CUs and the proj GEMM in front of it is
-        # better off as a launch of its own over all of them (C5, 2 064 rows: 6.39 ms separate, 6.44 fused)
-        w1t, w2t = _mlp_weights(sd, p, wc)
-        wp = sd[p + "attn.proj.weight"]
-        wpt = wc.derived(("vit_proj_tiled", p), (wp,), lambda: ops.vit_proj_retile(wc.get(wp)))
-        return ops.vit_mlp(xs, w1t, sd[p + "mlp.fc1.bias"], w2t, sd[p + "mlp.fc2.bias"],
-                           (sd[p + "norm2.weight"], sd[p + "norm2.bias"]), row_scale=dp2, row_scale_rows=Tn,
-                           residual2=pos if add_pos_out else None, proj=(a, wpt, sd[p + "attn.proj.bias"], dp1, Tn))
-    ops.gemm(a, wc.get(sd[p + "attn.proj.weight"]), out=x_mid, bias=sd[p + "attn.proj.bias"], row_scale=dp1,
-             row_scale_rows=Tn, residual=xs)
-    if fused_mlp:
-        # frozen block: LayerNorm + fc1 + GELU + fc2 + DropPath + residual (+ the next block's "+ pos") in one kernel
-        w1t, w2t = _mlp_weights(sd, p, wc)
-        return ops.vit_mlp(x_mid, w1t, sd[p + "mlp.fc1.bias"], w2t, sd[p + "mlp.fc2.bias"],
-                           (sd[p + "norm2.weight"], sd[p + "norm2.bias"]), row_scale=dp2, row_scale_rows=Tn,
-                           residual2=pos if add_pos_out else None)
-    h2, mean2, rstd2 = ops.layernorm_fwd(x_mid, sd[p + "norm2.weight"], sd[p + "norm2.bias"], T, save_stats=keep)
-    pre = torch.empty((x.shape[0], sd[p + "mlp.fc1.weight"].shape[0]), dtype=T, device=x.device) if keep else None
-    f = ops.gemm(h2, wc.get(sd[p + "mlp.fc1.weight"]), out_dtype=T, bias=sd[p + "mlp.fc1.bias"], act=ACT_GELU,
-                 out2=pre, out2_pre=True)
-    x_out = torch.empty_like(x) if keep else x_mid
+        h2, mean2, rstd2 = ops.layernorm_fwd(x_mid, *ln2, T, save_stats=keep)
+        pre = torch.empty((x.shape[0], sd[p + "mlp.fc1.weight"].shape[0]), dtype=T, device=x.device) if keep else None
+        f = ops.gemm(h2, wc.get(sd[p + "mlp.fc1.weight"]), out_dtype=T, bias=sd[p + "mlp.fc1.bias"], act=ACT_GELU,
+                     out2=pre, out2_pre=True)
+    x_out = stream()
     ops.gemm(f, wc.get(sd[p + "mlp.fc2.weight"]), out=x_out, bias=sd[p + "mlp.fc2.bias"], row_scale=dp2,
-             row_scale_rows=Tn, residual=x_mid, residual2=pos if add_pos_out else None)
+             row_scale_rows=Tn, residual=x_mid, residual2=res2)
     if keep:
         save.update(xs=xs, mean1=mean1, rstd1=rstd1, h=h, qkv=qkv, a=a, lse=lse, x_mid=x_mid, mean2=mean2,
                     rstd2=rstd2, h2=h2, pre=pre, f=f, dp1=dp1, dp2=dp2)
@@ -863,7 +849,9 @@ def pointmlp_forward(sd, p, wc, pc, fps_starts, train, drop_masks, update_runnin
 TEXT_FUSE_LN = os.environ.get("PPT_TEXT_FUSE_LN", "0") != "0"
 # round 5: the text tower's K = 2048 / 1536 linears (c_proj forward; the dX products of c_fc and in_proj) as split-K launches whose
 # partial products are summed by the LayerNorm kernel that consumes them (ops.gemm_splitk + ops.layernorm_fwd_sum / _bwd_sum).
-# 16-bit operand modes only: the fp32 parity mode keeps the single-launch summation order.
+# 16-bit operand modes and split16 only: the fp32 parity mode keeps the single-launch summation order.  c_proj with 817 rows is 104
+# workgroups walking 32 K slabs each at ONE CU's L2 -> LDS rate (~9 of its 12.6 us); as four K slices it is 416 workgroups of 8 slabs,
+# and the LayerNorm that reads the result anyway adds the four fp32 partial products up with the residual and the bias: no reduction launch.
 TEXT_SPLITK = os.environ.get("PPT_TEXT_SPLITK", "1") != "0"
 # PointMLP's LocalGrouper normalisation as two launches per stage (csrc/pointmlp.hip: cloud_rstd_kernel, pointmlp_pq_kernel) instead of
 # ~25 ATen ones; PPT_POINTMLP_FUSED_NORM=0: the ATen expressions (A/B, bit-identity test).
@@ -887,8 +875,32 @@ TEXT_MLP_PAIR_SPLIT = os.environ.get("PPT_TEXT_MLP_PAIR_SPLIT", "1") != "0"
 TEXT_LIN_SPLIT = os.environ.get("PPT_TEXT_LIN_SPLIT", "1") != "0"
 
 
-def _text_lin_ok(Ta, width):
-    return TEXT_LIN_SPLIT and width == 512 and (Ta in ops.HALF or (Ta == torch.float32 and ops.split16_enabled()))
+_TextPlan = collections.namedtuple("_TextPlan", "fuse splitk lin_split bwd_splitk bwd_lin_split pair_ok")
+
+
+def _text_plan(T, Ta, Tm, M, Wd, split16):
+    """Which kernels the layers of the text tower run on, forward and backward; reads the switches when called.  T: the tower's
+    operand dtype, Ta / Tm: the attention / MLP half's (diagnostics: _stage_wc), M rows, split16 = ops.split16_enabled().
+      fuse       LayerNorm -> in_proj / c_fc as one rowgemm launch (TEXT_FUSE_LN)
+      splitk     c_proj as four K slices, handed to the next layer's LayerNorm (TEXT_SPLITK); 16-bit modes and split16
+      lin_split  in_proj / out_proj on csrc/text_lin.hip
+      pair_ok    the MLP half may be ONE ops.text_mlp_pair launch (_text_pair decides per layer)
+    The backward's pair differs from the forward's, as it always has: no kernel of the backward has a LayerNorm prologue, so `fuse`
+    does not hold its split-K back; that split-K covers dX products of BOTH halves (c_fc: K = 2048, in_proj: K = 1536), so both must
+    run on the tower's dtype, not the MLP half alone; and text-lin yields in_proj's dX as K / 512 partial products, which only the
+    split-K form's LayerNorm backward adds up, where the forward's K = 512 products need no hand-over (split16 runs without one)."""
+    half = T in ops.HALF
+    fuse = TEXT_FUSE_LN and half and Wd in ops.ROWGEMM_K and Ta == T and Tm == T
+    splitk = TEXT_SPLITK and (half or split16) and Tm == T and M <= 4096 and Wd == 512
+    lin_ok = TEXT_LIN_SPLIT and Wd == 512 and (Ta in ops.HALF or (Ta == torch.float32 and split16))
+    pair_ok = TEXT_MLP_PAIR and (Tm in ops.HALF or (Tm == torch.float32 and TEXT_MLP_PAIR_SPLIT and split16))
+    return _TextPlan(fuse=fuse, splitk=splitk and not fuse, lin_split=lin_ok and not fuse and (Ta == torch.float32 or splitk),
+                     bwd_splitk=splitk and Ta == T, bwd_lin_split=lin_ok and splitk and Ta == T, pair_ok=pair_ok)
+
+
+def _text_pair(plan, splitk, sd, p, last=False):
+    """The MLP half of layer `p` as ONE text_mlp_pair launch?  splitk: plan.splitk / plan.bwd_splitk, the hand-over its products need."""
+    return plan.pair_ok and splitk and (not last or TEXT_MLP_PAIR_LAST) and tuple(sd[p + "mlp.c_fc.weight"].shape) == (2048, 512)
 
 
 def _text_lin_tiles(sd, name, wca, transposed=False):
@@ -911,8 +923,13 @@ def _text_lin(a, sd, name, wca, transposed=False, **kw):
     return ops.text_lin16(a, wt, **kw) if wca.dtype in ops.HALF else ops.text_lin_split(a, wt, **kw)
 
 
-def _text_mlp_pair_ok(Tm):
-    return Tm in ops.HALF or (Tm == torch.float32 and TEXT_MLP_PAIR_SPLIT and ops.split16_enabled())
+def _attn_linear(a, sd, name, wca, lin_split, transposed=False, **kw):
+    """a @ W^T (transposed: a @ W) of the attention half: on the text-lin kernel or the tile GEMM; in wca's dtype unless out= is given."""
+    if lin_split:
+        return _text_lin(a, sd, name, wca, transposed, **kw)
+    if "out" not in kw:
+        kw["out_dtype"] = wca.dtype
+    return ops.gemm(a, wca.get(sd[name], "wt" if transposed else "w"), **kw)
 
 
 def _text_mlp_tiles(sd, p, wcm, backward):
@@ -940,6 +957,65 @@ def _text_mlp(a, sd, p, wcm, *, pre=None, backward=False, save=False):
     return ops.text_mlp_pair(h2, w1t, w2t, bias=sd[p + "mlp.c_fc.bias"], pre=pre), mean2, rstd2
 
 
+def _ln_stats(x, save):
+    """(mean, rstd) buffers for a LayerNorm applied inside another kernel's prologue, or None"""
+    return tuple(torch.empty((x.shape[0],), dtype=torch.float32, device=x.device) for _ in range(2)) if save else None
+
+
+def _text_in_proj(sd, p, wca, plan, x, add, add_rows, pending, save, ly):
+    """ln_1 + in_proj of layer `p` -> qkv.  ly["x"]: the layer's input as the residual stream holds it -- x; with add (the first
+    layer) x + add[row % add_rows]; with pending = (x_mid, c_proj bias, partial products) of the previous layer its output, which
+    this layer's LayerNorm forms and writes out."""
+    ln1 = (sd[p + "ln_1.weight"], sd[p + "ln_1.bias"])
+    if plan.fuse and add is None:
+        # LayerNorm applied while the rows are staged (one node of the prompt chain instead of two); its statistics kept for the backward
+        st1 = _ln_stats(x, save)
+        ly.update(x=x, mean1=st1 and st1[0], rstd1=st1 and st1[1])
+        return ops.rowgemm(x, wca.get(sd[p + "attn.in_proj_weight"]), ln=ln1, ln_stats=st1, bias=sd[p + "attn.in_proj_bias"])
+    if pending is not None:
+        xs = torch.empty_like(pending[0])
+        h, mean1, rstd1 = ops.layernorm_fwd_sum(*pending, *ln1, wca.dtype, write_xs=xs, save_stats=save)
+    else:
+        xs = x if add is None else torch.empty_like(x)
+        h, mean1, rstd1 = ops.layernorm_fwd(x, *ln1, wca.dtype, add=add, add_rows=add_rows, write_xs=xs if add is not None else None,
+                                            save_stats=save)
+    ly.update(x=xs, mean1=mean1, rstd1=rstd1)
+    return _attn_linear(h, sd, p + "attn.in_proj_weight", wca, plan.lin_split, bias=sd[p + "attn.in_proj_bias"])
+
+
+def _text_mlp_half(sd, p, wcm, plan, x_mid, last, save, ly):
+    """ln_2 + c_fc + QuickGELU + c_proj + residual of layer `p` -> (x, None): the layer's output, or (None, pending): what the next
+    layer's LayerNorm forms it from (_text_in_proj)."""
+    Tm, bias, ln2 = wcm.dtype, sd[p + "mlp.c_proj.bias"], (sd[p + "ln_2.weight"], sd[p + "ln_2.bias"])
+    pre = torch.empty((x_mid.shape[0], sd[p + "mlp.c_fc.weight"].shape[0]), dtype=Tm, device=x_mid.device) if save else None
+    parts = None
+    if _text_pair(plan, plan.splitk, sd, p, last):
+        # c_fc + QuickGELU + c_proj in one launch: eight partial products, handed over like split-K's four
+        parts, mean2, rstd2 = _text_mlp(x_mid, sd, p, wcm, pre=pre, save=save)
+    elif plan.fuse:
+        st2 = _ln_stats(x_mid, save)
+        mean2, rstd2 = st2 or (None, None)
+        f = ops.rowgemm(x_mid, wcm.get(sd[p + "mlp.c_fc.weight"]), ln=ln2, ln_stats=st2, bias=sd[p + "mlp.c_fc.bias"], act=ACT_QUICKGELU,
+                        out2=pre)
+    else:
+        h2, mean2, rstd2 = ops.layernorm_fwd(x_mid, *ln2, Tm, save_stats=save)
+        f = ops.gemm(h2, wcm.get(sd[p + "mlp.c_fc.weight"]), out_dtype=Tm, bias=sd[p + "mlp.c_fc.bias"], act=ACT_QUICKGELU, out2=pre,
+                     out2_pre=True)
+    ly.update(x_mid=x_mid, mean2=mean2, rstd2=rstd2, pre=pre)
+    if parts is None and plan.splitk and not last:
+        parts = ops.gemm_splitk(f, wcm.get(sd[p + "mlp.c_proj.weight"]), 4)
+    if parts is not None and not last:
+        return None, (x_mid, bias, parts)
+    x = torch.empty_like(x_mid)
+    if parts is None:
+        ops.gemm(f, wcm.get(sd[p + "mlp.c_proj.weight"]), out=x, bias=bias, residual=x_mid)
+    else:
+        # (the LAST layer has no LayerNorm of a next layer to add its partial products up: ln_final's launch over all rows does it --
+        # its normalised output is not used, the summed rows are; split16: 2 x 41 us of tile GEMMs -> 23 + 6 us)
+        ops.layernorm_fwd_sum(x_mid, bias, parts, sd["ln_final.weight"], sd["ln_final.bias"], torch.float32, write_xs=x)
+    return x, None
+
+
 def text_tower_forward(sd, wc, prompts, eot_pos, heads, layers, save, eff_len=None, prefix=0, rows_in=None):
     """encode_text: prompts [C,L,W] fp32 -> text features [C,E] fp32 (before L2 normalisation).
     save=True keeps what the input-gradient backward needs.
@@ -960,7 +1036,6 @@ def text_tower_forward(sd, wc, prompts, eot_pos, heads, layers, save, eff_len=No
     rows_in = (x0 [M, W] f32, C, Lfull): the first layer's input ALREADY in the tower's row layout with the positional
     embedding added (ops.prompt_rows builds it from the learnable tokens in one kernel); `prompts` is then None and the
     backward hands back the gradient of x0 as it is."""
-    T = wc.dtype
     if rows_in is not None:
         x0, C, Lfull = rows_in
         Wd = x0.shape[1]
@@ -991,99 +1066,23 @@ def text_tower_forward(sd, wc, prompts, eot_pos, heads, layers, save, eff_len=No
         xin = prompts.reshape(M, Wd)
         rows = torch.arange(C, device=dev) * L + eot_pos            # EOT pooling (ULIP_models.py:222)
     saved = {"layers": []} if save else None
-    x = xin if add is None else torch.empty((M, Wd), dtype=torch.float32, device=dev)
-    fuse = TEXT_FUSE_LN and T in ops.HALF and Wd in ops.ROWGEMM_K
     # (diagnostics, tools/bf16_error.py: the attention half and the MLP half of every layer may run at another operand precision;
     # both start from and end in the fp32 residual stream)
     wca, wcm = _stage_wc(wc, "text_attn"), _stage_wc(wc, "text_mlp")
-    Ta, Tm = wca.dtype, wcm.dtype
-    if Ta != T or Tm != T:
-        fuse = False
-
-    def stats():
-        return (torch.empty((M,), dtype=torch.float32, device=dev), torch.empty((M,), dtype=torch.float32, device=dev)) if save else None
-    # split-K for the K = 2048 linear (c_proj): with 817 rows it is 104 workgroups walking 32 K slabs each at ONE CU's L2 -> LDS rate
-    # (~9 of its 12.6 us); as four K slices it is 416 workgroups of 8 slabs, and the four fp32 partial products are added up -- with
-    # the residual and the bias -- by the LayerNorm that reads the result anyway (ops.layernorm_fwd_sum): no reduction launch.
-    # (16-bit modes and split16; the fp32 parity mode keeps the single-launch summation order)
-    splitk = TEXT_SPLITK and (T in ops.HALF or ops.split16_enabled()) and Tm == T and not fuse and M <= 4096 and Wd == 512
-    lin_split = _text_lin_ok(Ta, Wd) and not fuse and (Ta == torch.float32 or splitk)
-    pending = None                  # (x_mid, c_proj bias, partial products) of the previous layer: its output is formed by this layer's LN1
+    plan = _text_plan(wc.dtype, wca.dtype, wcm.dtype, M, Wd, ops.split16_enabled())
+    x, pending = xin, None
     for i in range(layers):
         p = f"transformer.resblocks.{i}."
-        if pending is not None:
-            x = torch.empty((M, Wd), dtype=torch.float32, device=dev)
-            h, mean1, rstd1 = ops.layernorm_fwd_sum(pending[0], pending[1], pending[2], sd[p + "ln_1.weight"], sd[p + "ln_1.bias"], Ta,
-                                                    write_xs=x, save_stats=save)
-            pending = None
-            if lin_split:
-                qkv = _text_lin(h, sd, p + "attn.in_proj_weight", wca, bias=sd[p + "attn.in_proj_bias"])
-            else:
-                qkv = ops.gemm(h, wca.get(sd[p + "attn.in_proj_weight"]), out_dtype=Ta, bias=sd[p + "attn.in_proj_bias"])
-        elif fuse and add is None:
-            # LayerNorm applied while the rows are staged (one node of the prompt chain instead of two); its statistics are
-            # kept for the backward
-            st1 = stats()
-            mean1, rstd1 = st1 if save else (None, None)
-            qkv = ops.rowgemm(xin, wc.get(sd[p + "attn.in_proj_weight"]), ln=(sd[p + "ln_1.weight"], sd[p + "ln_1.bias"]), ln_stats=st1,
-                              bias=sd[p + "attn.in_proj_bias"])
-        else:
-            h, mean1, rstd1 = ops.layernorm_fwd(xin, sd[p + "ln_1.weight"], sd[p + "ln_1.bias"], Ta, add=add,
-                                                add_rows=add_rows, write_xs=x if add is not None else None,
-                                                save_stats=save)
-            if lin_split:
-                qkv = _text_lin(h, sd, p + "attn.in_proj_weight", wca, bias=sd[p + "attn.in_proj_bias"])
-            else:
-                qkv = ops.gemm(h, wca.get(sd[p + "attn.in_proj_weight"]), out_dtype=Ta, bias=sd[p + "attn.in_proj_bias"])
-        add, add_rows = None, 0
-        if P:
-            a, lse = ops.attention_prefix_fwd(qkv, C, L, P, heads, ATTN_SCALE, want_lse=save)
-        else:
-            a, lse = ops.attention_fwd(qkv, C, L, heads, ATTN_SCALE, True, want_lse=save)
-        x_mid = torch.empty_like(x)
-        if lin_split:
-            _text_lin(a, sd, p + "attn.out_proj.weight", wca, bias=sd[p + "attn.out_proj.bias"], residual=x, out=x_mid)
-        else:
-            ops.gemm(a, wca.get(sd[p + "attn.out_proj.weight"]), out=x_mid, bias=sd[p + "attn.out_proj.bias"], residual=x)
-        pre = torch.empty((M, sd[p + "mlp.c_fc.weight"].shape[0]), dtype=Tm, device=dev) if save else None
-        # (the LAST layer has no LayerNorm of a next layer to add its partial products up: ln_final's launch over all rows does it --
-        # its normalised output is not used, the summed rows are; split16: 2 x 41 us of tile GEMMs -> 23 + 6 us)
-        pair = (TEXT_MLP_PAIR and splitk and (i + 1 < layers or TEXT_MLP_PAIR_LAST) and _text_mlp_pair_ok(Tm)
-                and tuple(sd[p + "mlp.c_fc.weight"].shape) == (2048, 512))
-        if pair:
-            # c_fc + QuickGELU + c_proj in one launch; its eight partial products are this layer's output once the next layer's
-            # LayerNorm has added them to x_mid and the bias (the split-K hand-over below, with 8 slices instead of 4)
-            parts, mean2, rstd2 = _text_mlp(x_mid, sd, p, wcm, pre=pre, save=save)
-            if save:
-                saved["layers"].append(dict(x=x, mean1=mean1, rstd1=rstd1, qkv=qkv, a=a, lse=lse, x_mid=x_mid, mean2=mean2,
-                                            rstd2=rstd2, pre=pre))
-            if i + 1 < layers:
-                pending = (x_mid, sd[p + "mlp.c_proj.bias"], parts)
-            else:
-                x = torch.empty_like(x_mid)
-                ops.layernorm_fwd_sum(x_mid, sd[p + "mlp.c_proj.bias"], parts, sd["ln_final.weight"], sd["ln_final.bias"], torch.float32,
-                                      write_xs=x)
-                xin = x
-            continue
-        if fuse:
-            st2 = stats()
-            mean2, rstd2 = st2 if save else (None, None)
-            f = ops.rowgemm(x_mid, wc.get(sd[p + "mlp.c_fc.weight"]), ln=(sd[p + "ln_2.weight"], sd[p + "ln_2.bias"]), ln_stats=st2,
-                            bias=sd[p + "mlp.c_fc.bias"], act=ACT_QUICKGELU, out2=pre)
-        else:
-            h2, mean2, rstd2 = ops.layernorm_fwd(x_mid, sd[p + "ln_2.weight"], sd[p + "ln_2.bias"], Tm, save_stats=save)
-            f = ops.gemm(h2, wcm.get(sd[p + "mlp.c_fc.weight"]), out_dtype=Tm, bias=sd[p + "mlp.c_fc.bias"],
-                         act=ACT_QUICKGELU, out2=pre, out2_pre=True)
+        ly = {}
+        qkv = _text_in_proj(sd, p, wca, plan, x, add, add_rows, pending, save, ly)
+        a, lse = (ops.attention_prefix_fwd(qkv, C, L, P, heads, ATTN_SCALE, want_lse=save) if P else
+                  ops.attention_fwd(qkv, C, L, heads, ATTN_SCALE, True, want_lse=save))
+        x_mid = torch.empty_like(ly["x"])
+        _attn_linear(a, sd, p + "attn.out_proj.weight", wca, plan.lin_split, bias=sd[p + "attn.out_proj.bias"], residual=ly["x"], out=x_mid)
+        x, pending = _text_mlp_half(sd, p, wcm, plan, x_mid, i + 1 == layers, save, ly)
         if save:
-            saved["layers"].append(dict(x=x, mean1=mean1, rstd1=rstd1, qkv=qkv, a=a, lse=lse, x_mid=x_mid, mean2=mean2,
-                                        rstd2=rstd2, pre=pre))
-        if splitk and i + 1 < layers:
-            pending = (x_mid, sd[p + "mlp.c_proj.bias"], ops.gemm_splitk(f, wcm.get(sd[p + "mlp.c_proj.weight"]), 4))
-            continue
-        x_next = torch.empty_like(x)
-        ops.gemm(f, wcm.get(sd[p + "mlp.c_proj.weight"]), out=x_next, bias=sd[p + "mlp.c_proj.bias"], residual=x_mid)
-        x = x_next
-        xin = x
+            saved["layers"].append(dict(ly, qkv=qkv, a=a, lse=lse))
+        add, add_rows = None, 0
     x_eot = x.index_select(0, rows)
     hn, meanf, rstdf = ops.layernorm_fwd(x_eot, sd["ln_final.weight"], sd["ln_final.bias"], torch.float32,
                                          save_stats=save)
@@ -1109,6 +1108,41 @@ def _f32_cache(wc):
     return c[1]
 
 
+def _text_ln_bwd(d, x, w, mean, rstd, g, copy_dtype):
+    """The LayerNorm backward that ends a half of a layer: its input gradient is added to g (the residual stream's gradient);
+    -> g's new value in copy_dtype, the next half's operand.  d: the output gradient [M, D], or its partial products [S, M, D]."""
+    if d.dim() == 3:
+        return ops.layernorm_bwd_sum(d, x, w, mean, rstd, g, accumulate=True, copy_dtype=copy_dtype)[1]
+    return ops.layernorm_bwd(d, x, w, mean, rstd, dx=g, accumulate=True, copy_dtype=copy_dtype)[3]
+
+
+def _text_mlp_half_bwd(sd, p, wca, wcm, plan, ly, g, g_t):
+    if _text_pair(plan, plan.bwd_splitk, sd, p):
+        # the branch's input gradient ((g W_proj) * QuickGELU'(pre)) W_fc in one launch: eight partial products
+        d = _text_mlp(g_t, sd, p, wcm, pre=ly["pre"], backward=True)
+    else:
+        d_pre = ops.gemm(g_t, wcm.get(sd[p + "mlp.c_proj.weight"], "wt"), out_dtype=wcm.dtype, act=ACT_QUICKGELU, dact_pre=ly["pre"])
+        if plan.bwd_splitk:         # K = 2048 over 817 rows: four K slices (see _text_plan)
+            d = ops.gemm_splitk(d_pre, wcm.get(sd[p + "mlp.c_fc.weight"], "wt"), 4)
+        else:
+            d = ops.gemm(d_pre, wcm.get(sd[p + "mlp.c_fc.weight"], "wt"), out_dtype=torch.float32)
+    return _text_ln_bwd(d, ly["x_mid"], sd[p + "ln_2.weight"], ly["mean2"], ly["rstd2"], g, wca.dtype)
+
+
+def _text_attn_half_bwd(sd, p, wca, wcm, plan, ly, g, g_t, s):
+    C, L, heads, P = s["C"], s["L"], s["heads"], s["P"]
+    d_a = _attn_linear(g_t, sd, p + "attn.out_proj.weight", wca, plan.bwd_lin_split, True)
+    d_qkv = (ops.attention_prefix_bwd(ly["qkv"], ly["a"], d_a, ly["lse"], C, L, P, heads, ATTN_SCALE) if P else
+             ops.attention_bwd(ly["qkv"], ly["a"], d_a, ly["lse"], C, L, heads, ATTN_SCALE, True))
+    if plan.bwd_lin_split:          # K = 1536: three partial products either way
+        d = _text_lin(d_qkv, sd, p + "attn.in_proj_weight", wca, True)
+    elif plan.bwd_splitk:
+        d = ops.gemm_splitk(d_qkv, wca.get(sd[p + "attn.in_proj_weight"], "wt"), 3)
+    else:
+        d = ops.gemm(d_qkv, wca.get(sd[p + "attn.in_proj_weight"], "wt"), out_dtype=torch.float32)
+    return _text_ln_bwd(d, ly["x"], sd[p + "ln_1.weight"], ly["mean1"], ly["rstd1"], g, wcm.dtype)
+
+
 def text_tower_backward(sd, wc, s, dout, grad_scale=1.0):
     """Input gradient of encode_text: dout [C,E] -> d prompts [C,L,W] fp32.  The tower is frozen
     (ULIP_models.py:487-507), so no weight gradient is ever formed: 4 dX GEMMs, 2 LayerNorm
@@ -1119,9 +1153,8 @@ def text_tower_backward(sd, wc, s, dout, grad_scale=1.0):
     gradient enters them multiplied by the power of two S -- folded into the very first product, d_hn = S * dout @ P^T -- and
     leaves multiplied by 1 / S: in the row-layout mode by the CALLER (ops.prompt_rows_bwd(..., scale = 1 / S) folds it into the
     kernel that sums the rows onto the tokens; the returned g is still scaled), otherwise here."""
-    T = wc.dtype
     S = float(grad_scale)
-    C, L, Wd, heads, P, M = s["C"], s["L"], s["W"], s["heads"], s["P"], s["M"]
+    C, L, Wd, P, M = s["C"], s["L"], s["W"], s["P"], s["M"]
     wc32 = _f32_cache(wc)
     d_hn = ops.rows_matmul(dout.contiguous(), wc32.get(sd["text_projection"], "wt"), alpha=S) if dout.shape[0] <= 256 else None
     if d_hn is None:
@@ -1130,49 +1163,12 @@ def text_tower_backward(sd, wc, s, dout, grad_scale=1.0):
     g = torch.zeros((M, Wd), dtype=torch.float32, device=dout.device)
     g.index_copy_(0, s["rows"], d_eot)
     wca, wcm = s.get("wca", wc), s.get("wcm", wc)              # (per-half operand precision: diagnostics, see the forward)
-    Ta, Tm = wca.dtype, wcm.dtype
-    splitk = TEXT_SPLITK and (T in ops.HALF or ops.split16_enabled()) and Ta == T and Tm == T and M <= 4096 and Wd == 512
-    lin_split = _text_lin_ok(Ta, Wd) and splitk and Tm == Ta
-    g_t = ops.convert(g, Tm)
+    plan = _text_plan(wc.dtype, wca.dtype, wcm.dtype, M, Wd, ops.split16_enabled())
+    g_t = ops.convert(g, wcm.dtype)
     for i in reversed(range(len(s["layers"]))):
         p = f"transformer.resblocks.{i}."
-        ly = s["layers"][i]
-        if TEXT_MLP_PAIR and splitk and _text_mlp_pair_ok(Tm) and tuple(sd[p + "mlp.c_fc.weight"].shape) == (2048, 512):
-            # the branch's input gradient ((g W_proj) * QuickGELU'(pre)) W_fc in one launch: eight partial products, added up by the
-            # LayerNorm backward that reads them
-            _, g_t = ops.layernorm_bwd_sum(_text_mlp(g_t, sd, p, wcm, pre=ly["pre"], backward=True), ly["x_mid"],
-                                           sd[p + "ln_2.weight"], ly["mean2"], ly["rstd2"], g, accumulate=True, copy_dtype=Ta)
-            d_pre = None
-        else:
-            d_pre = ops.gemm(g_t, wcm.get(sd[p + "mlp.c_proj.weight"], "wt"), out_dtype=Tm, act=ACT_QUICKGELU,
-                             dact_pre=ly["pre"])
-        if d_pre is None:
-            pass
-        elif splitk:
-            # K = 2048 over 817 rows: four K slices, added up by the LayerNorm backward that reads the product (see the forward)
-            _, g_t = ops.layernorm_bwd_sum(ops.gemm_splitk(d_pre, wcm.get(sd[p + "mlp.c_fc.weight"], "wt"), 4), ly["x_mid"],
-                                           sd[p + "ln_2.weight"], ly["mean2"], ly["rstd2"], g, accumulate=True, copy_dtype=Ta)
-        else:
-            d_h2 = ops.gemm(d_pre, wcm.get(sd[p + "mlp.c_fc.weight"], "wt"), out_dtype=torch.float32)
-            _, _, _, g_t = ops.layernorm_bwd(d_h2, ly["x_mid"], sd[p + "ln_2.weight"], ly["mean2"], ly["rstd2"], dx=g,
-                                             accumulate=True, copy_dtype=Ta)
-        if lin_split:
-            d_a = _text_lin(g_t, sd, p + "attn.out_proj.weight", wca, True)
-        else:
-            d_a = ops.gemm(g_t, wca.get(sd[p + "attn.out_proj.weight"], "wt"), out_dtype=Ta)
-        if P:
-            d_qkv = ops.attention_prefix_bwd(ly["qkv"], ly["a"], d_a, ly["lse"], C, L, P, heads, ATTN_SCALE)
-        else:
-            d_qkv = ops.attention_bwd(ly["qkv"], ly["a"], d_a, ly["lse"], C, L, heads, ATTN_SCALE, True)
-        if splitk:                  # K = 1536: three slices
-            dparts = (_text_lin(d_qkv, sd, p + "attn.in_proj_weight", wca, True) if lin_split
-                      else ops.gemm_splitk(d_qkv, wca.get(sd[p + "attn.in_proj_weight"], "wt"), 3))
-            _, g_t = ops.layernorm_bwd_sum(dparts, ly["x"],
-                                           sd[p + "ln_1.weight"], ly["mean1"], ly["rstd1"], g, accumulate=True, copy_dtype=Tm)
-        else:
-            d_h = ops.gemm(d_qkv, wca.get(sd[p + "attn.in_proj_weight"], "wt"), out_dtype=torch.float32)
-            _, _, _, g_t = ops.layernorm_bwd(d_h, ly["x"], sd[p + "ln_1.weight"], ly["mean1"], ly["rstd1"], dx=g,
-                                             accumulate=True, copy_dtype=Tm)
+        g_t = _text_mlp_half_bwd(sd, p, wca, wcm, plan, s["layers"][i], g, g_t)
+        g_t = _text_attn_half_bwd(sd, p, wca, wcm, plan, s["layers"][i], g, g_t, s)
     if s["rows_mode"]:
         return g                                            # gradient of the row-layout input, STILL scaled by S (ops.prompt_rows_bwd folds it and 1 / S)
     if S != 1.0:
