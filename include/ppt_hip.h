@@ -50,7 +50,8 @@ const char *ppt_strerror(int code);
  *    ppt_text_lin16 / ppt_text_lin_retile16 (the 16-bit form of ppt_text_lin_split); ppt_cloud_prep_f32 / ppt_cloud_draws (csrc/cloud_prep.hip);
  *    ppt_cls_metrics / ppt_partseg_metrics / ppt_partseg_metrics_chunks (csrc/metrics.hip);
  *    ppt_logreg_fit_f32 / ppt_logreg_predict_f32 / ppt_logreg_workspace_bytes (csrc/logreg.hip);
- *    ppt_nearest_rows_f32 / ppt_nearest_rows_workspace_bytes (csrc/nearest.hip).
+ *    ppt_nearest_rows_f32 / ppt_nearest_rows_workspace_bytes (csrc/nearest.hip);
+ *    ppt_partseg_predict / ppt_render_balls / ppt_render_balls_workspace_bytes (csrc/render.hip).
  * 6: ppt_gemm_params.split16 / split_a_pow2 / split_b_pow2 (new trailing fields: fp32 operands as hi + lo half pairs),
  *    ppt_attention_fwd_split16 / ppt_attention_bwd_split16 (new), ppt_pointmlp_cloud_rstd / ppt_pointmlp_pq (new).
  * 5: ppt_labels_check (new), ppt_gemm256 (new: the 256-row macro-tile GEMM core), ppt_set_gemm256 / ppt_get_gemm256 (new),
@@ -853,6 +854,43 @@ int ppt_logreg_predict_f32(const float *feat, int64_t ld, int Nbank, const int32
 size_t ppt_nearest_rows_workspace_bytes(int Q, int V, int D, int k);
 int ppt_nearest_rows_f32(const float *q, int Q, const float *table, int64_t ld, int V, int D, int k, int32_t *idx, float *dist,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- part-seg pictures (ABI 7, additive; csrc/render.hip; host side: ppt_amd/viz.py) ---------------------------------------------
+ * What notebook/show_balls.py shows of a part-segmentation model: the per-point predictions (:256-262) and shaded-ball pictures
+ * of ground truth and prediction (:94-131, its call into a prebuilt render_ball), headless and for whole batches.  Nothing is
+ * allocated, nothing synchronises; no global atomics: two runs write identical bytes.
+ *
+ * partseg_predict replaces show_balls.py:256-262 (main_partseg.py:300-305): the masked arg-max, per point.
+ *   logits [B, N, P] f32; anchor [B] i64: a part id that names the cloud's category (the reference passes labels[b, 0]);
+ *   part_start / part_count [P] int32 as for ppt_partseg_metrics.
+ *   -> pred [B, N] int32: the first arg-max over the category's part range [start, start + count), plus start -- the rule
+ *   ppt_partseg_metrics counts by; -1 for every point of a cloud whose anchor lies outside [0, P) (or whose range is empty).
+ *   P <= 64: PPT_EUNSUPPORTED otherwise (nothing launched); B <= 65535.
+ *
+ * render_balls replaces render_ball: every point is drawn as a shaded ball, the nearest ball wins the pixel.
+ *   ixyz [G, n, 3] int32: the points of G geometries in pixel space -- row, column, depth (larger = nearer), |depth| < 2^30;
+ *   colors [G, K, n, 3] f32 in [0, 255]: K colourings of each geometry (visibility is resolved once and shaded K times);
+ *   background: a HOST array of 3 bytes (it travels by value with the launch); radius: r = max(radius, 1);
+ *   pattern [(2 r - 1)^2, 2] f64 DEVICE array, entry (dx + r - 1) (2 r - 1) + (dy + r - 1): dz = sqrt((double)(r^2 - dx^2 - dy^2))
+ *   and the shade s = dz / r where dx^2 + dy^2 < r^2 (strictly), dz < 0 elsewhere.  The caller computes it on the host, in
+ *   double, so that no device rounding of sqrt enters a pixel.
+ *   -> out [G, K, H, W, 3] u8, channel c from colour channel c (RGB in, RGB out).  The rule:
+ *     point i at (x, y, z) offers the depth z2 = (int)(z + dz), computed in double and truncated toward zero, to every pixel
+ *     (x + dx, y + dy) of its pattern that lies inside the image; a pixel goes to the largest z2, equal z2 to the LOWEST point
+ *     index (what a sequential loop over the points with a strict `<` depth test leaves); a pixel nobody reaches is `background`;
+ *     with zmin = min_i z - r and zmax = max_i z + r over all n points of the geometry (off-screen ones included),
+ *     intensity = min(1.0, (z2 - zmin) / (zmax - zmin) * 0.7 + 0.3), and the value is (unsigned char)(s * (double)colour *
+ *     intensity) -- every step in double, in this order, without contraction.  n = 0 draws the background only (ixyz and
+ *     colors may then be NULL).
+ *   workspace: ppt_render_balls_workspace_bytes(G, n, H, W, radius) bytes, 256-byte aligned (0 for an unsupported shape): the depth
+ *   range of every geometry.
+ *   radius <= 16, H, W <= 4096, n <= 65536: PPT_EUNSUPPORTED outside (nothing launched); NULL pointers, non-positive G, K, H, W,
+ *   n < 0 or a short workspace: PPT_EINVAL. */
+int ppt_partseg_predict(const float *logits, const int64_t *anchor, int B, int N, int P, const int32_t *part_start,
+                        const int32_t *part_count, int32_t *pred, void *stream);
+size_t ppt_render_balls_workspace_bytes(int G, int n, int H, int W, int radius);
+int ppt_render_balls(const int32_t *ixyz, const float *colors, const double *pattern, const unsigned char *background, int radius,
+                     int G, int K, int n, int H, int W, unsigned char *out, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

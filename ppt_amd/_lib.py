@@ -253,6 +253,10 @@ _SIGNATURES = {
     "ppt_nearest_rows_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
     "ppt_nearest_rows_f32": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                      ctypes.c_size_t, c_void_p]),
+    "ppt_partseg_predict": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ppt_render_balls_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "ppt_render_balls": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_char_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                 c_void_p, ctypes.c_size_t, c_void_p]),
 }
 
 

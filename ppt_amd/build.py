@@ -24,7 +24,9 @@ COMMON = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-
           "-fno-gpu-rdc"] + ([] if os.environ.get("PPT_SLP") == "1" else ["-fno-slp-vectorize"])
 PER_FILE = {"fps.hip": ["-ffp-contract=off"], "knn_group.hip": ["-ffp-contract=off"],
             # the input pipeline reproduces numpy bit for bit: no contraction, IEEE-rounded fp32 `/` and sqrtf (hipcc's default, pinned)
-            "cloud_prep.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]}
+            "cloud_prep.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+            # the renderer's pixel values are a stated sequence of double operations: no fused multiply-add
+            "render.hip": ["-ffp-contract=off"]}
 
 
 def sources():

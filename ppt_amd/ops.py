@@ -1281,6 +1281,82 @@ def partseg_metrics(logits, labels, smoothing, part_start, part_count, max_parts
                                               int(max_parts), _p(records), _p(partial), _stream()), "ppt_partseg_metrics")
 
 
+def partseg_predict(logits, anchor, part_start, part_count, pred=None):
+    """logits [B, N, P] f32, anchor [B] i64 (a part id that names the cloud's category: labels[:, 0]), part_start / part_count
+    [P] i32 as for partseg_metrics -> pred [B, N] i32 (caller-owned, allocated when None): the first arg-max over the category's
+    part range, plus its start -- the rule partseg_metrics counts by; -1 for a cloud whose anchor is outside [0, P)
+    (ppt_partseg_predict)."""
+    _chk(logits, torch.float32, "logits"); _chk(anchor, torch.int64, "anchor"); _chk(pred, torch.int32, "pred")
+    _chk(part_start, torch.int32, "part_start"); _chk(part_count, torch.int32, "part_count")
+    B, N, P = logits.shape
+    if pred is None:
+        pred = torch.empty((B, N), dtype=torch.int32, device=logits.device)
+    assert anchor.shape == (B,) and pred.shape == (B, N) and part_start.numel() == P and part_count.numel() == P
+    _lib.check(_lib.lib().ppt_partseg_predict(_p(logits), _p(anchor), B, N, P, _p(part_start), _p(part_count), _p(pred), _stream()),
+               "ppt_partseg_predict")
+    return pred
+
+
+RENDER_MAX_RADIUS, RENDER_MAX_IMAGE, RENDER_MAX_POINTS = 16, 4096, 65536        # limits of ppt_render_balls (include/ppt_hip.h)
+_BALL_PATTERNS = {}
+
+
+def ball_pattern_host(radius):
+    """The ball of ppt_render_balls as a host array [(2 r - 1)^2, 2] f64, r = max(radius, 1): per offset (dx, dy), row-major over
+    dx, the depth dz = sqrt(r^2 - dx^2 - dy^2) and the shade dz / r inside the circle dx^2 + dy^2 < r^2; dz = -1 outside."""
+    import numpy as np
+    r = max(int(radius), 1)
+    d = np.arange(-(r - 1), r, dtype=np.int64)
+    rest = r * r - d[:, None] ** 2 - d[None, :] ** 2
+    dz = np.sqrt(np.maximum(rest, 0).astype(np.float64))
+    table = np.stack([dz, dz / float(r)], -1)
+    table[rest <= 0] = (-1.0, 0.0)
+    return np.ascontiguousarray(table.reshape(-1, 2))
+
+
+def _ball_pattern(radius, device):
+    key = (max(int(radius), 1), str(device))
+    if key not in _BALL_PATTERNS:                   # (host -> device once per radius and device; nothing is read back)
+        _BALL_PATTERNS[key] = torch.from_numpy(ball_pattern_host(radius)).to(device)
+    return _BALL_PATTERNS[key]
+
+
+def render_balls_workspace_bytes(G, n, H, W, radius):
+    """bytes of scratch ppt_render_balls needs for G geometries of n points on H x W pictures (0: unsupported shape)"""
+    return _lib.lib().ppt_render_balls_workspace_bytes(int(G), int(n), int(H), int(W), int(radius))
+
+
+def render_balls(ixyz, colors, H, W, radius, background=(255, 255, 255), out=None, workspace=None):
+    """ixyz [G, n, 3] i32 (row, column, depth), colors [G, K, n, 3] f32 in [0, 255] -> out [G, K, H, W, 3] u8 (caller-owned,
+    allocated when None): every point a shaded ball of the given radius, the nearest wins the pixel, equal depths go to the lower
+    point index, untouched pixels are `background` (ppt_render_balls; the rule: include/ppt_hip.h).  The visibility of a geometry
+    is resolved once for its K colourings.  workspace: a caller-owned uint8 tensor of at least
+    render_balls_workspace_bytes(G, n, H, W, radius) bytes (allocated when None)."""
+    _chk(ixyz, torch.int32, "ixyz"); _chk(colors, torch.float32, "colors"); _chk(out, torch.uint8, "out")
+    _chk(workspace, torch.uint8, "workspace")
+    if ixyz.dim() != 3 or ixyz.shape[2] != 3 or colors.dim() != 4 or colors.shape[3] != 3:
+        raise RuntimeError("render_balls: ixyz must be [G, n, 3] and colors [G, K, n, 3]")
+    G, n, _ = ixyz.shape
+    K = colors.shape[1]
+    H, W, radius = int(H), int(W), int(radius)
+    assert colors.shape[0] == G and colors.shape[2] == n
+    bg = bytes(int(c) & 0xFF for c in background)
+    assert len(bg) == 3
+    need = _lib.lib().ppt_render_balls_workspace_bytes(G, n, H, W, radius)
+    if need == 0:
+        raise RuntimeError(f"render_balls: unsupported shape G={G} n={n} H={H} W={W} radius={radius} (G, H, W >= 1, radius <= "
+                           f"{RENDER_MAX_RADIUS}, H, W <= {RENDER_MAX_IMAGE}, n <= {RENDER_MAX_POINTS})")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=ixyz.device)
+    if out is None:
+        out = torch.empty((G, K, H, W, 3), dtype=torch.uint8, device=ixyz.device)
+    assert out.shape == (G, K, H, W, 3)
+    pattern = _ball_pattern(radius, ixyz.device)
+    _lib.check(_lib.lib().ppt_render_balls(_p(ixyz) if n else None, _p(colors) if n else None, _p(pattern), bg, radius, G, K, n, H, W,
+                                           _p(out), _p(workspace), workspace.numel(), _stream()), "ppt_render_balls")
+    return out
+
+
 LOGREG_INFO = 8                                     # words of a fit's info record (include/ppt_hip.h)
 LOGREG_CONVERGED, LOGREG_MAXITER, LOGREG_LINESEARCH, LOGREG_BADINPUT = 0, 1, 2, 3
 
