@@ -892,6 +892,61 @@ size_t ppt_render_balls_workspace_bytes(int G, int n, int H, int W, int radius);
 int ppt_render_balls(const int32_t *ixyz, const float *colors, const double *pattern, const unsigned char *background, int radius,
                      int G, int K, int n, int H, int W, unsigned char *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- feature-distribution figure: exact t-SNE (ABI 7, additive; csrc/tsne.hip; host side: ppt_amd/tsne.py) ------------------------
+ * What the "Feature Distribution" cells of notebook/visualize.ipynb ask of sklearn.manifold.TSNE(n_components=2) on the logits
+ * that save_recog_feats writes, as the exact O(N^2) algorithm in two output dimensions.  Every entry takes device pointers and a
+ * stream; nothing is allocated, nothing synchronises; no atomics and a fixed summation order: two runs write identical bytes.
+ * The statement below is this project's own; parity with sklearn's coordinates is not claimed (the optimisation is chaotic).
+ * All arithmetic is uncontracted (no fused multiply-add); fp32 unless it says double.
+ *
+ * tsne_affinities (once per run): x [N, ld >= D] f32 -> P [N, ldp >= N] f32, beta [N] f32, pstats [2] double.
+ *   d_ij = sum_c (x_ic - x_jc)^2, accumulated over the columns c in ascending order: d_ij == d_ji bit for bit, a duplicate row
+ *   is at distance exactly 0.
+ *   For row i over j != i: m_i = min_j d_ij, e_ij = d_ij - m_i, q_ij(beta) = expf(-(beta * e_ij)),
+ *     S = sum_j q_ij (>= 1),  A = sum_j e_ij * q_ij,  H(beta) = log S + beta * A / S   (the entropy of the row, in nats).
+ *   S and A: every thread sums its terms (j = thread, thread + 256, ...) in fp32, the 256 thread sums are combined in double by
+ *   a fixed tree, and H is evaluated in double.  beta_i comes from the search of sklearn's _binary_search_perplexity: beta = 1,
+ *   lo = -inf, hi = +inf; at most 100 steps; stop when |H - log(perplexity)| <= 1e-5; if H is too large lo = beta and beta
+ *   doubles while hi = +inf, else becomes (beta + hi) / 2; if H is too small hi = beta and beta halves while lo = -inf, else
+ *   becomes (beta + lo) / 2 (fp32).  A row that does not converge keeps the beta of its 100th evaluation.
+ *   p_{j|i} = q_ij(beta_i) / (float)S;  P_ij = (p_{j|i} + p_{i|j}) / (float)(2 N), an IEEE fp32 division;  P_ii = 0.
+ *   P is symmetric bit for bit; columns >= N of a row are never written.  pstats[0] = sum P_ij, pstats[1] = sum_{P_ij > 0} P_ij
+ *   logf(P_ij): per-tile sums in double, folded in tile order by one workgroup.
+ *   One workgroup per row keeps the row's distances in LDS for all 100 reductions; the conditional rows are written into P
+ *   and a tiled transpose-add (one workgroup per pair of mirrored 32 x 32 tiles) symmetrises P in place.
+ *   workspace: ppt_tsne_affinities_workspace_bytes(N, D) bytes, 256-byte aligned (0 for an unsupported shape).
+ *   x 4-byte aligned (16-byte aligned rows, ld % 4 == 0, take a vector path with the same bits); P 16-byte aligned, ldp % 4 == 0.
+ *
+ * tsne_steps enqueues iterations t = t0 .. t0 + n - 1 of the descent, two launches each, in one host call; the exaggeration
+ * alpha_t = (t < t_switch ? early_exaggeration : 1) and the momentum mu_t = (t < t_switch ? 0.5 : 0.8) travel by value.
+ *   y, update, gains [N, 2] f32 (the state, updated in place); P, pstats from tsne_affinities.
+ *   Pair pass (one wave per row i; Y is held in LDS, N * 8 bytes; P is read once, 16 bytes per lane along j): with
+ *     dx = y_i0 - y_j0, dy = y_i1 - y_j1, w_ij = rcp((dx * dx + dy * dy) + 1) (v_rcp_f32, 1 ulp) for j != i, w_ii = 0,
+ *     a_i = sum_j (P_ij w_ij) (dx, dy),  r_i = sum_j (w_ij w_ij) (dx, dy),  z_i = sum_j w_ij,  l_i = sum_j P_ij logf((dx dx + dy dy) + 1):
+ *   lane L sums the terms j = 4 L .. 4 L + 3, 4 L + 256 .. in ascending order, the 64 lane sums are folded by a butterfly
+ *   (xor 32, 16, 8, 4, 2, 1).  l_i is formed on check iterations only.
+ *   Update (one thread per i): Z = the double sum of all z_i in a fixed order (every workgroup re-reduces the N row sums),
+ *     g_i = 4 * (alpha * a_i - r_i * (float)(1 / Z)),
+ *     inc = update * g < 0;  gains = inc ? gains + 0.2 : gains * 0.8;  gains = max(gains, 0.01);
+ *     update = mu * update - lr * (g * gains);  y += update     (sklearn's _gradient_descent, elementwise, in this order).
+ *   On iterations with (t + 1) % check_every == 0 (check_every = 0: never) the next row of stats [stats_rows, 2] f32 is written
+ *   (the first check iteration of the call writes row 0): [0] KL_t = sum_{P_ij > 0} alpha P_ij log(alpha P_ij Z / w_ij), formed in
+ *   double as alpha (pstats[1] + pstats[0] (log alpha + log Z) + sum_i l_i);  [1] ||g||_2, from the double sum of g^2 in a fixed order.
+ *   grad (optional, [N, 2] f32): g of the LAST iteration of the call.
+ *   workspace: ppt_tsne_steps_workspace_bytes(N) bytes, 256-byte aligned (0 for an unsupported shape).  After a call it holds
+ *   the row sums of the last iteration: (a_i, r_i) [N, 4] f32, then z_i [N] f32, then l_i [N] f32 (check iterations), each array
+ *   starting on a 256-byte boundary.
+ * Limits: 2 <= N <= 16384 (Y in LDS), 1 <= D <= 4096 (the row staged in LDS), two output dimensions: PPT_EUNSUPPORTED outside,
+ * nothing launched.  NULL pointers, misalignment, non-positive sizes, ld < D, ldp < N, perplexity or lr not positive and finite,
+ * t0 < 0, n < 1, check_every < 0, too few stats rows or a short workspace: PPT_EINVAL. */
+size_t ppt_tsne_affinities_workspace_bytes(int N, int D);
+int ppt_tsne_affinities(const float *x, int64_t ld, int N, int D, float perplexity, float *P, int64_t ldp, float *beta,
+                        double *pstats, void *workspace, size_t workspace_bytes, void *stream);
+size_t ppt_tsne_steps_workspace_bytes(int N);
+int ppt_tsne_steps(const float *P, int64_t ldp, const double *pstats, int N, float *y, float *update, float *gains, int t0, int n,
+                   int t_switch, float early_exaggeration, float lr, int check_every, float *stats, int stats_rows, float *grad,
+                   void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -257,6 +257,12 @@ _SIGNATURES = {
     "ppt_render_balls_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "ppt_render_balls": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_char_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                  c_void_p, ctypes.c_size_t, c_void_p]),
+    "ppt_tsne_affinities_workspace_bytes": (ctypes.c_size_t, [c_int, c_int]),
+    "ppt_tsne_affinities": (c_int, [c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                    ctypes.c_size_t, c_void_p]),
+    "ppt_tsne_steps_workspace_bytes": (ctypes.c_size_t, [c_int]),
+    "ppt_tsne_steps": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
+                               c_int, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
 }
 
 

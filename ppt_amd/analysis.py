@@ -7,6 +7,8 @@ and the test set's logits for the notebook (save_recog_feats.py).
     save_recog_feats("modelnet40_test_feats_labels.pt", logits, labels, names)    # save_recog_feats.py:75-78 (same payload)
     python -m ppt_amd.analysis interpret --fpath checkpoint_best.pt --topk 10 [--dataset_name modelnet40 --bpe_path FILE]
     python -m ppt_amd.analysis logits --fpath checkpoint_best.pt --data test.npz --out feats.pt [--dataset_name ... --head_type 2]
+    feats, labels, names = load_recog_feats("modelnet40_test_feats_labels.pt")     # the payload back (visualize.ipynb's torch.load)
+    python -m ppt_amd.analysis tsne --feats feats.pt --out mn40_feats.png [--coords y.npz --perplexity 30 --n_iter 1000 --seed 0]
 
 The reference forms torch.cdist(ctx, token_embedding), a [M, 49408] matrix, and argsorts all of its columns for the first
 topk; here csrc/nearest.hip reads the table once and keeps the k best per token (ops.nearest_rows).  The distances are the
@@ -102,6 +104,43 @@ def save_recog_feats(path, logits, labels, names):
     return payload
 
 
+def load_recog_feats(path):
+    """The payload of save_recog_feats (or of the reference's save_recog_feats.py) back from disk, as the notebook's
+    "Feature Distribution" cells read it: -> (test_feats float64 [n, C], test_labels int64 [n], test_names str [n] or None)"""
+    payload = torch.load(path, map_location="cpu", weights_only=False)
+    feats = np.asarray(payload['test_feats'], dtype=np.float64)
+    labels = np.asarray(payload['test_labels']).astype(np.int64).reshape(-1)
+    if feats.ndim != 2 or labels.shape[0] != feats.shape[0]:
+        raise ValueError(f"load_recog_feats: test_feats {feats.shape} and test_labels {labels.shape} do not belong together")
+    names = payload.get('test_names')
+    return feats, labels, None if names is None else np.asarray(names)
+
+
+def tsne_parser(sub):
+    p = sub.add_parser("tsne", help="the notebook's feature-distribution figure from a save_recog_feats file (ppt_amd.tsne)")
+    p.add_argument("--feats", required=True, help="the file `logits --out` (save_recog_feats) wrote")
+    p.add_argument("--out", required=True, help="the PNG to write")
+    p.add_argument("--coords", default=None, help="also write the embedding: .npz with Y [n, 2] f32, labels, kl_divergence")
+    p.add_argument("--perplexity", type=float, default=30.0)
+    p.add_argument("--n_iter", type=int, default=1000)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--size", type=int, default=1000)
+    p.add_argument("--radius", type=int, default=6)
+    return p
+
+
+def tsne_figure(a):
+    """`python -m ppt_amd.analysis tsne`: payload -> embedding on the device -> PNG (+ the coordinates)"""
+    from . import tsne as T, viz
+    feats, labels, _ = load_recog_feats(a.feats)
+    Y, info = T.tsne(feats, perplexity=a.perplexity, n_iter=a.n_iter, seed=a.seed)
+    viz.save_png(a.out, T.feature_scatter(Y, labels, size=a.size, radius=a.radius))
+    if a.coords:
+        np.savez(a.coords, Y=Y.cpu().numpy(), labels=labels, kl_divergence=np.float64(info["kl_divergence"]))
+    print(f"=> {feats.shape[0]} points, KL divergence {info['kl_divergence']:.4f} after {info['n_iter']} iterations: {a.out}")
+    return Y, info
+
+
 def _build_model(a):
     from types import SimpleNamespace
     from .models import ULIP_models as M
@@ -132,7 +171,10 @@ def main(argv=None):
             p.add_argument("--npoints", type=int, default=1024)
             p.add_argument("--batch_size", type=int, default=32)
             p.add_argument("--out", required=True)
+    tsne_parser(sub)
     a = ap.parse_args(argv)
+    if a.command == "tsne":
+        return tsne_figure(a)
     state = torch.load(a.fpath, map_location="cpu", weights_only=False)
     model, args = _build_model(a)
     if a.command == "interpret":

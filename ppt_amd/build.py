@@ -26,7 +26,9 @@ PER_FILE = {"fps.hip": ["-ffp-contract=off"], "knn_group.hip": ["-ffp-contract=o
             # the input pipeline reproduces numpy bit for bit: no contraction, IEEE-rounded fp32 `/` and sqrtf (hipcc's default, pinned)
             "cloud_prep.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
             # the renderer's pixel values are a stated sequence of double operations: no fused multiply-add
-            "render.hip": ["-ffp-contract=off"]}
+            "render.hip": ["-ffp-contract=off"],
+            # t-SNE: the descent step equals its numpy restatement bit for bit, and d_ij == d_ji needs one rounding per operation
+            "tsne.hip": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -1435,6 +1435,70 @@ def nearest_rows_workspace_bytes(Q, V, D, k):
     return _lib.lib().ppt_nearest_rows_workspace_bytes(int(Q), int(V), int(D), int(k))
 
 
+TSNE_MAX_N, TSNE_MAX_D = 16384, 4096               # limits of ppt_tsne_affinities / ppt_tsne_steps (include/ppt_hip.h)
+
+
+def tsne_affinities_workspace_bytes(N, D):
+    """bytes of scratch ppt_tsne_affinities needs for N rows of D columns (0: unsupported shape)"""
+    return _lib.lib().ppt_tsne_affinities_workspace_bytes(int(N), int(D))
+
+
+def tsne_steps_workspace_bytes(N):
+    """bytes of scratch ppt_tsne_steps needs for N points (0: unsupported shape)"""
+    return _lib.lib().ppt_tsne_steps_workspace_bytes(int(N))
+
+
+def tsne_affinities(x, perplexity, d=None, P=None, workspace=None):
+    """x [N, >= D] f32 (padded rows allowed) -> (P [N, ldp] f32 -- a view [N, N] of a matrix whose row stride is a multiple of
+    four --, beta [N] f32, pstats [2] f64: sum P and sum P log P): the symmetric joint probabilities of exact t-SNE at the given
+    perplexity (ppt_tsne_affinities; the statement: include/ppt_hip.h).  P, workspace: caller-owned (allocated when None)."""
+    if not x.is_cuda:
+        raise RuntimeError("tsne_affinities: x: expected a CUDA/HIP tensor (ppt_amd has no CPU path)")
+    D = x.shape[1] if d is None else int(d)
+    ld, N = _bank(x, D)
+    need = _lib.lib().ppt_tsne_affinities_workspace_bytes(N, D)
+    if need == 0:
+        raise RuntimeError(f"tsne_affinities: unsupported shape N={N} D={D} (2 <= N <= {TSNE_MAX_N}, 1 <= D <= {TSNE_MAX_D})")
+    if P is None:
+        P = torch.empty((N, (N + 3) & ~3), dtype=torch.float32, device=x.device)[:, :N]
+    if not P.is_cuda or P.dtype != torch.float32 or P.shape != (N, N) or P.stride(1) != 1:
+        raise RuntimeError("tsne_affinities: P must be a CUDA/HIP f32 matrix [N, N] with contiguous rows")
+    _chk(workspace, torch.uint8, "workspace")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    beta = torch.empty(N, dtype=torch.float32, device=x.device)
+    pstats = torch.empty(2, dtype=torch.float64, device=x.device)
+    _lib.check(_lib.lib().ppt_tsne_affinities(_p(x), ld, N, D, float(perplexity), _p(P), P.stride(0), _p(beta), _p(pstats), _p(workspace),
+                                              workspace.numel(), _stream()), "ppt_tsne_affinities")
+    return P, beta, pstats
+
+
+def tsne_steps(P, pstats, y, update, gains, t0, n, *, t_switch=250, early_exaggeration=12.0, lr, check_every=0, stats=None, grad=None,
+               workspace=None):
+    """Iterations t0 .. t0 + n - 1 of the t-SNE descent on the state y, update, gains [N, 2] f32 (in place), enqueued by one call
+    (ppt_tsne_steps): exaggeration `early_exaggeration` and momentum 0.5 while t < t_switch, then 1 and 0.8.  check_every > 0:
+    every iteration with (t + 1) % check_every == 0 writes (KL, ||g||) to the next row of stats [rows, 2] f32, from row 0.
+    grad [N, 2] f32 (optional) receives the gradient of the last iteration.  Nothing is read back.  -> y"""
+    for name, t in (("y", y), ("update", update), ("gains", gains), ("grad", grad), ("stats", stats)):
+        _chk(t, torch.float32, name)
+    _chk(pstats, torch.float64, "pstats"); _chk(workspace, torch.uint8, "workspace")
+    N = y.shape[0]
+    if not P.is_cuda or P.dtype != torch.float32 or P.shape != (N, N) or P.stride(1) != 1:
+        raise RuntimeError("tsne_steps: P must be a CUDA/HIP f32 matrix [N, N] with contiguous rows")
+    assert y.shape == (N, 2) and update.shape == (N, 2) and gains.shape == (N, 2) and (grad is None or grad.shape == (N, 2))
+    need = _lib.lib().ppt_tsne_steps_workspace_bytes(N)
+    if need == 0:
+        raise RuntimeError(f"tsne_steps: unsupported N={N} (2 <= N <= {TSNE_MAX_N})")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=y.device)
+    rows = 0 if stats is None else stats.shape[0]
+    assert stats is None or (stats.dim() == 2 and stats.shape[1] == 2)
+    _lib.check(_lib.lib().ppt_tsne_steps(_p(P), P.stride(0), _p(pstats), N, _p(y), _p(update), _p(gains), int(t0), int(n), int(t_switch),
+                                         float(early_exaggeration), float(lr), int(check_every), _p(stats), rows, _p(grad),
+                                         _p(workspace), workspace.numel(), _stream()), "ppt_tsne_steps")
+    return y
+
+
 def health_check(x, flags, bit, maxabs=None):
     """flags[0] |= bit if x (any dtype, contiguous) holds a non-finite value; maxabs[0] = max(maxabs[0], max |finite x|) when
     given (ppt_health_check).  flags: int32 [1]; maxabs: f32 [1], non-negative."""
