@@ -51,7 +51,9 @@ const char *ppt_strerror(int code);
  *    ppt_cls_metrics / ppt_partseg_metrics / ppt_partseg_metrics_chunks (csrc/metrics.hip);
  *    ppt_logreg_fit_f32 / ppt_logreg_predict_f32 / ppt_logreg_workspace_bytes (csrc/logreg.hip);
  *    ppt_nearest_rows_f32 / ppt_nearest_rows_workspace_bytes (csrc/nearest.hip);
- *    ppt_partseg_predict / ppt_render_balls / ppt_render_balls_workspace_bytes (csrc/render.hip).
+ *    ppt_partseg_predict / ppt_render_balls / ppt_render_balls_workspace_bytes (csrc/render.hip);
+ *    ppt_attention_ragged_fwd (csrc/attention_ragged.hip); ppt_sentence_rows / ppt_template_ensemble / ppt_cosine_head
+ *    (csrc/zeroshot.hip).
  * 6: ppt_gemm_params.split16 / split_a_pow2 / split_b_pow2 (new trailing fields: fp32 operands as hi + lo half pairs),
  *    ppt_attention_fwd_split16 / ppt_attention_bwd_split16 (new), ppt_pointmlp_cloud_rstd / ppt_pointmlp_pq (new).
  * 5: ppt_labels_check (new), ppt_gemm256 (new: the 256-row macro-tile GEMM core), ppt_set_gemm256 / ppt_get_gemm256 (new),
@@ -946,6 +948,43 @@ size_t ppt_tsne_steps_workspace_bytes(int N);
 int ppt_tsne_steps(const float *P, int64_t ldp, const double *pstats, int N, float *y, float *update, float *gains, int t0, int n,
                    int t_switch, float early_exaggeration, float lr, int check_every, float *stats, int stats_rows, float *grad,
                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- zero-shot classification: the CLIP text tower on ragged sentence rows (csrc/attention_ragged.hip, csrc/zeroshot.hip) ----
+ * The reference pads every sentence to 77 positions and pools at argmax of its token ids (ULIP_models.py:203-222).  Here
+ * sentence s of S, with len_s = argmax(ids[s]) + 1 positions, owns rows [off[s], off[s + 1]) of every [M, ...] row tensor of the
+ * tower, off = cumsum(len): row off[s] + p is position p, row off[s + 1] - 1 its EOT; positions behind the EOT are not stored
+ * (the mask is causal: they influence nothing).  Rows [off[S], M) are padding that belongs to no sentence.
+ *
+ * sentence_rows: replaces token_embedding(tokenized) (ULIP_models.py:102) + the positional add of encode_text (:209):
+ *   out[off[s] + p] = table[ids[s, p]] + pos[p], fp32, one launch; rows [off[S], rows) = 0.  table [vocab, W], pos [>= max len, W],
+ *   ids [S, ctx] i32, offsets [S + 1] i32, out [rows, W]; W % 4 == 0, 16-byte aligned table / pos / out.  An id outside
+ *   [0, vocab) gives a zero row (the host wrapper refuses such ids before the launch).
+ *
+ * attention_ragged_fwd: replaces nn.MultiheadAttention (ULIP_models.py:38,49-51) under the causal mask (:224-230) for the ragged
+ *   layout.  qkv [M, 3, H, 64] as in_proj writes it -> out [M, H * 64]; dtype PPT_F32 (both products from hi + lo IEEE-half pairs
+ *   of the fp32 operands, as ppt_attention_fwd_split16), PPT_F16 or PPT_BF16; softmax statistics fp32; no LSE.  len_s <= 128.
+ *   plan [nbins * 64] i32 packs the sentences into bins of 64 virtual rows, one K / V tile each: entry (s << 8) | p for the
+ *   virtual row that is position p of sentence s, -1 for an empty one.  A sentence of at most 64 positions starts at a virtual
+ *   row that is a multiple of 16 and stays inside one bin; a longer one takes two bins of its own from row 0, and nothing else
+ *   shares them.  A workgroup takes two (bin, head) pairs.  Every sentence gets the bits ppt_attention_fwd (16-bit forms) /
+ *   ppt_attention_fwd_split16 give for it alone, wherever it lands; rows outside the plan are neither read nor written.
+ *   hd must be 64; qkv and out 16-byte aligned.
+ *
+ * template_ensemble: ULIP's zero-shot classifier: W[c] = normalize(mean over t in [goff[c], goff[c + 1]) of normalize(feat[t])).
+ *   feat [S, E] f32 (un-normalised text features), group_offsets [C + 1] i32 ascending with non-empty groups, W [C, E] f32.
+ *   One workgroup per class, sentences in ascending order, fixed reduction trees.  E <= 2048.  A range is clamped to [0, S]; an
+ *   empty one gives a zero row.
+ *
+ * cosine_head: logits[b, c] = exp(*logit_scale) * <f[b] / |f[b]|, W[c]>, fp32: the CLIP / ULIP rule.  (PPT's own forward,
+ *   ULIP_models.py:279-281, does not normalise the point feature.)  f [B, E], W [C, E], logit_scale one f32 on the device,
+ *   logits [B, C].  E <= 4096.
+ * NULL pointers, non-positive sizes, misalignment, an unknown dtype: PPT_EINVAL; E beyond the limits: PPT_EUNSUPPORTED. */
+int ppt_sentence_rows(const float *table, int vocab, const float *pos, const int *ids, int ctx, const int *offsets, int S, int W,
+                      float *out, int rows, void *stream);
+int ppt_attention_ragged_fwd(const void *qkv, void *out, const int *offsets, const int *plan, int S, int M, int nbins, int H, int hd,
+                             float scale, int dtype, void *stream);
+int ppt_template_ensemble(const float *feat, const int *group_offsets, int S, int C, int E, float *W, void *stream);
+int ppt_cosine_head(const float *f, const float *W, const float *logit_scale, int B, int C, int E, float *logits, void *stream);
 
 #ifdef __cplusplus
 }

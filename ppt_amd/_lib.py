@@ -263,6 +263,11 @@ _SIGNATURES = {
     "ppt_tsne_steps_workspace_bytes": (ctypes.c_size_t, [c_int]),
     "ppt_tsne_steps": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
                                c_int, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    "ppt_sentence_rows": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "ppt_attention_ragged_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
+                                         c_void_p]),
+    "ppt_template_ensemble": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ppt_cosine_head": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 

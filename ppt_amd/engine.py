@@ -1096,6 +1096,39 @@ def text_tower_forward(sd, wc, prompts, eot_pos, heads, layers, save, eff_len=No
     return out, saved
 
 
+def text_tower_forward_ragged(sd, wc, x0, offsets, max_len, heads, layers, plan=None):
+    """encode_text for sentences of DIFFERENT lengths, forward only: x0 [M, W] fp32 in the ragged row layout (sentence s owns rows
+    [offsets[s], offsets[s + 1]), position p at row offsets[s] + p, its EOT token at the last of them; the positional embedding
+    already added: ops.sentence_rows) -> text features [S, E] fp32 before L2 normalisation (ULIP_models.py:203-222 with :219's
+    argmax pooling per sentence).  offsets [S + 1] i32 on the device; max_len: the longest sentence (host).
+
+    LayerNorm, in_proj / out_proj and the MLP half work on rows and run through text_tower_forward's per-half helpers on the same
+    launch plan (_text_plan: M <= 4096 rows takes the prompt chain's kernels); only the attention knows the layout:
+    ops.attention_ragged_fwd (plan: ops.ragged_attention_plan of the lengths on the device; None: built from offsets with one
+    device read).  ln_final and text_projection run on the S EOT rows.  Rows behind offsets[S] (padding) belong to no sentence:
+    the attention leaves them as they are, every other kernel treats rows independently, and nothing reads them at the end."""
+    M, Wd = x0.shape
+    if not 0 < int(max_len) <= ops.RAGGED_MAX_LEN:
+        raise ValueError(f"text_tower_forward_ragged: sentences of 1 .. {ops.RAGGED_MAX_LEN} positions, got max_len = {max_len}")
+    wca, wcm = _stage_wc(wc, "text_attn"), _stage_wc(wc, "text_mlp")
+    tplan = _text_plan(wc.dtype, wca.dtype, wcm.dtype, M, Wd, ops.split16_enabled())
+    x, pending = x0, None
+    for i in range(layers):
+        p = f"transformer.resblocks.{i}."
+        ly = {}
+        qkv = _text_in_proj(sd, p, wca, tplan, x, None, 0, pending, False, ly)
+        a = ops.attention_ragged_fwd(qkv, offsets, heads, ATTN_SCALE, plan=plan)
+        x_mid = torch.empty_like(ly["x"])
+        _attn_linear(a, sd, p + "attn.out_proj.weight", wca, tplan.lin_split, bias=sd[p + "attn.out_proj.bias"], residual=ly["x"], out=x_mid)
+        x, pending = _text_mlp_half(sd, p, wcm, tplan, x_mid, i + 1 == layers, False, ly)
+    x_eot = x.index_select(0, offsets[1:].long() - 1)          # EOT pooling (ULIP_models.py:219): a sentence's last stored row
+    hn, _, _ = ops.layernorm_fwd(x_eot, sd["ln_final.weight"], sd["ln_final.bias"], torch.float32)
+    wc32 = _f32_cache(wc)
+    if hn.shape[0] <= 256:
+        return ops.rows_matmul(hn, wc32.get(sd["text_projection"], "f32"))
+    return ops.gemm(hn, wc32.get(sd["text_projection"], "wt"), out_dtype=torch.float32)
+
+
 _F32_CACHES = {}
 
 

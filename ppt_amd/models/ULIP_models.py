@@ -861,8 +861,20 @@ class ULIP_WITH_IMAGE(nn.Module):
 
     def encode_text(self, prompts, tokenized_prompts=None):
         """ULIP_models.py:203-222: prompts [C,77,W] -> [C,embed_dim].  General in `prompts`, as the reference: the shared-prefix
-        evaluation is used only when the tensor's leading positions really are the same for every class."""
+        evaluation is used only when the tensor's leading positions really are the same for every class.
+        (Pools at THIS model's tokenized_prompts; text with other EOT positions or another sentence count: encode_sentences.)"""
         return _TextTowerFn.apply(self, prompts, False)
+
+    def encode_sentences(self, token_ids, max_rows=None):
+        """Any tokenised text through the CLIP text tower: token_ids [S, ctx] (host integers, as the tokenizer returns them) ->
+        [S, embed_dim] fp32, un-normalised -- ULIP_models.py:203-222 applied to token_embedding(token_ids), each sentence pooled at
+        ITS argmax (:219).  Runs in the model's current precision mode on the text tower's operand format (_cache(): IEEE half in
+        "mixed16" unless calibrate_text_precision sent the tower to fp32 / split16), under no_grad, eager, in the ragged row layout
+        (ppt_amd/zeroshot.py, engine.text_tower_forward_ragged: nothing behind a sentence's EOT is stored).  Sentences are taken in
+        chunks of at most max_rows rows (None: zeroshot.DEFAULT_MAX_ROWS), a sentence is never split.  An empty list or an id
+        outside [0, vocab) raises ValueError before anything is launched."""
+        from .. import zeroshot
+        return zeroshot.encode_sentences(self, token_ids, max_rows)
 
     def _prefix_of(self, prompts, cand):
         """`cand` if positions 0 .. cand-1 of `prompts` [C,L,W] are identical in every class, else 0.  One host read per call:

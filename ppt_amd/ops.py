@@ -1668,6 +1668,99 @@ def prompt_rows_bwd(g, rows_of, n_tok, scale=1.0):
 
 
 # ---------------------------------------------------------------------------------------------
+# zero-shot classification: the text tower on ragged sentence rows (csrc/attention_ragged.hip, csrc/zeroshot.hip; ppt_amd/zeroshot.py)
+RAGGED_MAX_LEN = 128                 # positions of a sentence the ragged attention takes (two 64-key tiles); the tower's ctx is 77
+
+
+def ragged_attention_plan(lens):
+    """HOST: sentence lengths [S] -> the bin plan of ppt_attention_ragged_fwd, int32 numpy [nbins * 64]: entry (s << 8) | p for the
+    virtual row that is position p of sentence s, -1 for an empty one.  Sentences go into bins of 64 virtual rows in order, each
+    at a multiple of 16 rows and inside one bin (a new bin is opened when the next one does not fit); a sentence of 65-128
+    positions takes two bins of its own.  A function of the lengths alone: make it once per sentence set and pass it as `plan=`."""
+    import numpy as np
+    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+    if lens.size == 0 or int(lens.min()) < 1 or int(lens.max()) > RAGGED_MAX_LEN:
+        raise ValueError(f"ragged_attention_plan: every sentence needs 1 .. {RAGGED_MAX_LEN} positions")
+    start = np.empty(lens.size, dtype=np.int64)              # first virtual row of each sentence
+    fill = 0
+    for s, n in enumerate(lens.tolist()):
+        need = (n + 15) // 16 * 16 if n <= 64 else 128
+        if fill % 64 and (n > 64 or fill % 64 + need > 64):
+            fill = (fill + 63) // 64 * 64
+        start[s] = fill
+        fill += need
+    plan = np.full(((fill + 63) // 64) * 64, -1, dtype=np.int32)
+    sent = np.repeat(np.arange(lens.size, dtype=np.int64), lens)
+    pos = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens)
+    plan[start[sent] + pos] = ((sent << 8) | pos).astype(np.int32)
+    return plan
+
+
+def sentence_rows(table, pos, ids, offsets, rows):
+    """x0 [rows, W] f32: row offsets[s] + p = table[ids[s, p]] + pos[p] for the positions of sentence s, rows >= offsets[S] zero
+    (ppt_sentence_rows).  table [vocab, W] f32, pos [ctx, W] f32, ids [S, ctx] i32, offsets [S + 1] i32, all on the device."""
+    _chk(table, torch.float32, "table"); _chk(pos, torch.float32, "pos"); _chk(ids, torch.int32, "ids"); _chk(offsets, torch.int32, "offsets")
+    S, ctx = ids.shape
+    if offsets.numel() != S + 1 or pos.shape[0] < ctx or pos.shape[1] != table.shape[1]:
+        raise ValueError("sentence_rows: offsets must be [S + 1], pos [>= ctx, W]")
+    out = torch.empty((int(rows), table.shape[1]), dtype=torch.float32, device=table.device)
+    _lib.check(_lib.lib().ppt_sentence_rows(_p(table), table.shape[0], _p(pos), _p(ids), ctx, _p(offsets), S, table.shape[1], _p(out),
+                                            int(rows), _stream()), "ppt_sentence_rows")
+    return out
+
+
+def attention_ragged_fwd(qkv, offsets, H, scale, plan=None):
+    """causal attention of every sentence of the ragged layout: qkv [M, 3*H*64] (f32: split16 products; f16; bf16), offsets [S + 1]
+    i32 on the device -> out [M, H*64]; rows >= offsets[S] are left unwritten.  plan: ragged_attention_plan of the lengths as an
+    int32 DEVICE tensor; None builds it from offsets (one device read)."""
+    _chk(qkv, None, "qkv"); _chk(offsets, torch.int32, "offsets")
+    if plan is None:
+        o = offsets.cpu().numpy()
+        plan = torch.from_numpy(ragged_attention_plan(o[1:] - o[:-1])).to(qkv.device)
+    _chk(plan, torch.int32, "plan")
+    if qkv.dim() != 2 or qkv.shape[0] < 1 or qkv.shape[1] != 3 * H * 64:
+        raise ValueError(f"attention_ragged_fwd: qkv must be [M, 3 * H * 64] with H = {H}, got {tuple(qkv.shape)}")
+    if offsets.dim() != 1 or offsets.numel() < 2 or plan.dim() != 1 or plan.numel() == 0 or plan.numel() % 64:
+        raise ValueError("attention_ragged_fwd: offsets must be [S + 1], plan [bins * 64] (ragged_attention_plan)")
+    M = qkv.shape[0]
+    out = torch.empty((M, H * 64), dtype=qkv.dtype, device=qkv.device)
+    if profiler is not None:
+        profiler.begin("attention_ragged_fwd", 0.0)
+    _lib.check(_lib.lib().ppt_attention_ragged_fwd(_p(qkv), _p(out), _p(offsets), _p(plan), offsets.numel() - 1, M, plan.numel() // 64, H, 64,
+                                                   scale, dtype_code(qkv), _stream()), "ppt_attention_ragged_fwd")
+    if profiler is not None:
+        profiler.end()
+    return out
+
+
+def template_ensemble(feat, group_offsets):
+    """W [C, E] f32 = normalize(mean over the sentences of class c of normalize(feat[t])): ULIP's zero-shot classifier
+    (ppt_template_ensemble).  feat [S, E] f32, group_offsets [C + 1] i32 on the device, ascending within [0, S]; the values stay on the
+    device, so they are the caller's to check (zeroshot.classifier does, on the host): the kernel clamps a range to [0, S] and
+    writes a zero row for an empty one."""
+    _chk(feat, torch.float32, "feat"); _chk(group_offsets, torch.int32, "group_offsets")
+    if feat.dim() != 2 or feat.shape[0] < 1 or group_offsets.dim() != 1 or group_offsets.numel() < 2:
+        raise ValueError("template_ensemble: feat must be [S, E], group_offsets [C + 1]")
+    C = group_offsets.numel() - 1
+    W = torch.empty((C, feat.shape[1]), dtype=torch.float32, device=feat.device)
+    _lib.check(_lib.lib().ppt_template_ensemble(_p(feat), _p(group_offsets), feat.shape[0], C, feat.shape[1], _p(W), _stream()),
+               "ppt_template_ensemble")
+    return W
+
+
+def cosine_head(f, W, logit_scale):
+    """logits [B, C] = exp(logit_scale) * <f[b] / |f[b]|, W[c]>, fp32 (ppt_cosine_head): the CLIP / ULIP zero-shot rule -- unlike
+    PPT's own forward (ULIP_models.py:279-281) the point feature IS normalised.  logit_scale: a 0-dim f32 device tensor."""
+    _chk(f, torch.float32, "f"); _chk(W, torch.float32, "W"); _chk(logit_scale, torch.float32, "logit_scale")
+    if f.dim() != 2 or W.dim() != 2 or f.shape[1] != W.shape[1] or logit_scale.numel() != 1:
+        raise ValueError("cosine_head: f [B, E], W [C, E], logit_scale one value")
+    logits = torch.empty((f.shape[0], W.shape[0]), dtype=torch.float32, device=f.device)
+    _lib.check(_lib.lib().ppt_cosine_head(_p(f), _p(W), _p(logit_scale), f.shape[0], W.shape[0], f.shape[1], _p(logits), _stream()),
+               "ppt_cosine_head")
+    return logits
+
+
+# ---------------------------------------------------------------------------------------------
 # the device-resident input pipeline (csrc/cloud_prep.hip; ppt_amd/data/device_loader.py)
 def cloud_prep(src, item, n, *, sel=None, lengths=None, normalize=False, scale=None, shift=None, perm=None, seg_src=None):
     """src [M, Nmax, C >= 3] f32 resident clouds, item [B] i64 -> out [B, n, 3] f32 (and seg [B, n] i64 when seg_src [M, Nmax] i32
