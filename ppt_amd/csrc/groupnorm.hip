@@ -15,11 +15,17 @@ constexpr int GN_ROWS = 64;       // rows (q, k) per statistics workgroup
 constexpr int GN_Q = 32;          // query points per backward-sum workgroup
 constexpr int GN_MAXC = 1024;
 
+// The fp32 sums of a (chunk, channel) are CENTRED on the chunk's first row of that channel, k: sum (v - k) and sum (v - k)^2, terms
+// of the size of the spread, not of the mean.  The plain sum v and sum v^2 lost |mean| / std squared in relative accuracy before the
+// fp64 fold ever saw them (mean / std = 100: rstd off by 2.8e-4).  sum v = s + n k and sum v^2 = q + 2 k s + n k^2 are then formed in
+// fp64 per channel (by the thread that folded it), so the partials, their fold and gn_finish_kernel's S1 / n - mean^2 (all fp64) keep
+// their form.
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float *__restrict__ y, int R, int C, int G, double *__restrict__ part)
 {
-    __shared__ float ssum[GN_MAXC], ssq[GN_MAXC];
+    __shared__ double ssum[GN_MAXC], ssq[GN_MAXC];
     const int b = blockIdx.y, chunk = blockIdx.x, nch = gridDim.x;
     const int r0 = chunk * GN_ROWS, r1 = min(R, r0 + GN_ROWS);
+    const double nr = (double)(r1 - r0);
     if ((C & 3) == 0 && (((uintptr_t)y) & 15) == 0) {
         // 16 row groups x 16 column quads per pass of 64 columns: float4 loads (256-byte row pieces), the 16 group sums folded
         // through LDS in group order (the one-thread-per-column walk ran at 1.8 TB/s)
@@ -27,13 +33,15 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float *__restrict__
         const int q4 = threadIdx.x & 15, g = threadIdx.x >> 4;
         for (int c0 = 0; c0 < C; c0 += 64) {
             const int c = c0 + q4 * 4;
-            float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s;
+            float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s, ctr = s;
             if (c < C) {
+                ctr = *reinterpret_cast<const float4 *>(y + ((size_t)b * R + r0) * C + c);
 #pragma unroll 4
                 for (int r = r0 + g; r < r1; r += 16) {
                     const float4 v = *reinterpret_cast<const float4 *>(y + ((size_t)b * R + r) * C + c);
-                    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-                    q.x = fmaf(v.x, v.x, q.x); q.y = fmaf(v.y, v.y, q.y); q.z = fmaf(v.z, v.z, q.z); q.w = fmaf(v.w, v.w, q.w);
+                    const float4 d = make_float4(v.x - ctr.x, v.y - ctr.y, v.z - ctr.z, v.w - ctr.w);
+                    s.x += d.x; s.y += d.y; s.z += d.z; s.w += d.w;
+                    q.x = fmaf(d.x, d.x, q.x); q.y = fmaf(d.y, d.y, q.y); q.z = fmaf(d.z, d.z, q.z); q.w = fmaf(d.w, d.w, q.w);
                 }
             }
             rs[g][q4] = s; rq[g][q4] = q;
@@ -46,28 +54,34 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float *__restrict__
                     ts.x += a.x; ts.y += a.y; ts.z += a.z; ts.w += a.w;
                     tq.x += d.x; tq.y += d.y; tq.z += d.z; tq.w += d.w;
                 }
-                ssum[c] = ts.x; ssum[c + 1] = ts.y; ssum[c + 2] = ts.z; ssum[c + 3] = ts.w;
-                ssq[c] = tq.x; ssq[c + 1] = tq.y; ssq[c + 2] = tq.z; ssq[c + 3] = tq.w;
+                const float kk[4] = {ctr.x, ctr.y, ctr.z, ctr.w}, st[4] = {ts.x, ts.y, ts.z, ts.w}, qt[4] = {tq.x, tq.y, tq.z, tq.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const double kd = (double)kk[e], t = (double)st[e];
+                    ssum[c + e] = t + nr * kd;
+                    ssq[c + e] = (double)qt[e] + kd * (2.0 * t + nr * kd);
+                }
             }
             __syncthreads();
         }
     } else {
         for (int c = threadIdx.x; c < C; c += 256) {
+            const float k = y[((size_t)b * R + r0) * C + c];
             float s = 0.f, q = 0.f;
             for (int r = r0; r < r1; ++r) {
-                const float v = y[((size_t)b * R + r) * C + c];
-                s += v;
-                q = fmaf(v, v, q);
+                const float d = y[((size_t)b * R + r) * C + c] - k;
+                s += d;
+                q = fmaf(d, d, q);
             }
-            ssum[c] = s;
-            ssq[c] = q;
+            ssum[c] = (double)s + nr * (double)k;
+            ssq[c] = (double)q + (double)k * (2.0 * (double)s + nr * (double)k);
         }
     }
     __syncthreads();
     const int Cg = C / G;
     if ((int)threadIdx.x < G) {
         double s = 0.0, q = 0.0;
-        for (int c = threadIdx.x * Cg; c < ((int)threadIdx.x + 1) * Cg; ++c) { s += (double)ssum[c]; q += (double)ssq[c]; }
+        for (int c = threadIdx.x * Cg; c < ((int)threadIdx.x + 1) * Cg; ++c) { s += ssum[c]; q += ssq[c]; }
         double *o = part + (((size_t)b * nch + chunk) * G + threadIdx.x) * 2;
         o[0] = s;
         o[1] = q;

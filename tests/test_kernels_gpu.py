@@ -715,14 +715,19 @@ def test_ball_query_grouped_and_pointnet2_helpers(ops):
     assert (yb.cpu() - torch.relu(x.cpu() * sc.cpu() + sh.cpu()) * mk.cpu()).abs().max().item() < 1e-6
 
 
-@pytest.mark.parametrize("M,N1,N2", [(64, 64, 64), (32832, 384, 384), (32768, 1536, 384), (4096, 8, 72), (8192, 200, 136)])
-def test_gemm_tn_reads_operands_as_stored(ops, M, N1, N2):
-    """dW = dY^T X without transposed copies (ppt_gemm_tn_bf16): against fp64 on the same bf16 operands, for ragged
-    tile edges, row strides wider than the operand, and run-to-run bit reproducibility of the sliced reduction."""
+_GEMM_TN_SHAPES = [(64, 64, 64), (32832, 384, 384), (32768, 1536, 384), (4096, 8, 72), (8192, 200, 136)]
+
+
+@pytest.mark.parametrize("T,M,N1,N2", [pytest.param(torch.bfloat16, *s, id="%d-%d-%d" % s) for s in _GEMM_TN_SHAPES]
+                         + [pytest.param(torch.float16, *s, id="float16-%d-%d-%d" % s) for s in _GEMM_TN_SHAPES])
+def test_gemm_tn_reads_operands_as_stored(ops, T, M, N1, N2):
+    """dW = dY^T X without transposed copies (ppt_gemm_tn_half): against fp64 on the same 16-bit operands (bfloat16, and float16,
+    the format the decoder runs), for ragged tile edges, row strides wider than the operand, and run-to-run bit reproducibility of
+    the sliced reduction.  (The bound is one of fp32 accumulation of exact products: the same for both formats.)"""
     g = torch.Generator(device="cuda").manual_seed(M + N1)
-    a_full = torch.randn(M, N1 + 8, device="cuda", generator=g).to(torch.bfloat16)
+    a_full = torch.randn(M, N1 + 8, device="cuda", generator=g).to(T)
     a = a_full[:, :N1]                                                  # lda = N1 + 8
-    b = torch.randn(M, N2, device="cuda", generator=g).to(torch.bfloat16)
+    b = torch.randn(M, N2, device="cuda", generator=g).to(T)
     c = ops.gemm_tn_splitk(a, b)
     assert c.shape == (N1, N2) and c.dtype == torch.float32
     ref = a.double().t() @ b.double()
@@ -1049,7 +1054,8 @@ def test_rowgemm_rejects_what_it_does_not_support(ops):
 
 # ------------------------------------------------------------------ part-seg decoder glue (csrc/interp.hip)
 @pytest.mark.parametrize("B,N,S,D1,D2,dtype", [(2, 256, 512, 3, 384, torch.float32), (2, 2048, 512, 19, 384, torch.bfloat16),
-                                                (1, 100, 37, 0, 64, torch.float32), (3, 33, 64, 5, 130, torch.bfloat16)])
+                                                (1, 100, 37, 0, 64, torch.float32), (3, 33, 64, 5, 130, torch.bfloat16),
+                                                (2, 2048, 512, 19, 384, torch.float16), (3, 33, 64, 5, 130, torch.float16)])
 def test_three_nn_interp_fwd_matches_the_reference_formulation(ops, B, N, S, D1, D2, dtype):
     """ppt_three_nn_interp_fwd against pointnet2_utils.py:333-358 written with torch ops on the CPU (and the oracle's 3-NN):
     weights bit-exact up to the division's rounding, rows = [points1 | interpolated | 0] in the operand dtype."""
@@ -1061,7 +1067,7 @@ def test_three_nn_interp_fwd_matches_the_reference_formulation(ops, B, N, S, D1,
     idx, _, d = ops.knn_group(dev(xyz2), dev(xyz1), 3, want_nbhd=False, want_dist=True)
     oidx, ow = O.three_nn(xyz1, xyz2)
     assert np.array_equal(idx.cpu().numpy(), oidx)
-    mult = 8 if dtype == torch.bfloat16 else 4
+    mult = 8 if dtype in (torch.bfloat16, torch.float16) else 4
     rows, w = ops.three_nn_interp(p1.cuda() if D1 else None, p2.cuda(), idx, d, dtype, mult)
     assert np.abs(w.cpu().numpy() - ow).max() < 2e-6
     gathered = p2[torch.arange(B)[:, None, None], torch.from_numpy(oidx)]
@@ -1070,7 +1076,7 @@ def test_three_nn_interp_fwd_matches_the_reference_formulation(ops, B, N, S, D1,
     ld = (D1 + D2 + mult - 1) // mult * mult
     assert rows.shape == (B * N, ld)
     got = rows.float().cpu().view(B, N, ld)
-    tol = 1e-5 if dtype == torch.float32 else 2.0 ** -8
+    tol = 1e-5 if dtype == torch.float32 else _rel16(dtype, 2.0 ** -8)     # one rounding to the operand format
     assert (got[..., :D1 + D2] - want).abs().max().item() <= tol * max(1.0, want.abs().max().item())
     assert (got[..., D1 + D2:] == 0).all()
 
