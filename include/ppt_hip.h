@@ -158,6 +158,12 @@ typedef struct ppt_gemm_params {
     int pool_dtype;
     int pool_rows;                   /* 16, 32 or 64 (0 = 32): one kNN / ball-query group per pool_rows rows */
     void *pool_min;                  /* optional [M/pool_rows, N] minimum (BatchNorm with a negative scale flips the max) */
+    /* Statistics and pools exist in the register and the 16-byte epilogues only, so a launch that asks for either needs
+     * N % 8 == 0 and 16-byte aligned col_sum / col_sqsum / pool_max / pool_min, and everything the 16-byte walk touches must be
+     * 16-byte friendly: C aligned with ldc % 8 == 0, bias and group_add aligned, residual / residual2 / dact_pre / C2 aligned
+     * with ld % 8 == 0.  (A launch with a 16-bit or no C, no residual / dact_pre / row_scale / C2 and groups of 16 or a multiple
+     * of 32 rows runs the register epilogue, which reads bias and group_add one float at a time: there those two may sit at any
+     * 4-byte address.)  Anything else is PPT_EUNSUPPORTED, nothing launched. */
     /* batching (blockIdx.z): pointer offsets in ELEMENTS per batch */
     int batch; int64_t strideA, strideB, strideC;
     int wave_prio;                   /* != 0: the kernel raises its waves' issue priority (0: what ppt_set_wave_priority set) */

@@ -177,7 +177,7 @@ def _conv_bn_relu_fwd(xT, w, b, bn, training, prec, out_dtype, wprep=None):
     st = None
     if training and M % 32 == 0:
         st = (torch.empty((M // 32, N), dtype=torch.float32, device=xT.device), torch.empty((M // 32, N), dtype=torch.float32, device=xT.device))
-    y = ops.gemm(xT, wT, out_dtype=torch.float32, bias=b.detach().float().contiguous() if b is not None else None, col_stats=st)
+    y = ops.gemm(xT, wT, out_dtype=torch.float32, bias=ops.aligned16(b.detach().float().contiguous()) if b is not None else None, col_stats=st)
     g, be = bn.weight.detach().float().contiguous(), bn.bias.detach().float().contiguous()
     if training:
         parts, rpp = (st, 32) if st is not None else ops.rows_stats(y)

@@ -444,6 +444,10 @@ extern "C" int ppt_gemm(const ppt_gemm_params *pp, void *stream)
     if ((p.col_sum || p.pool_max) && ((p.N % 8) || ((uintptr_t)p.pool_min & 15) || ((uintptr_t)p.col_sum & 15) || ((uintptr_t)p.col_sqsum & 15) || ((uintptr_t)p.pool_max & 15)))
         return PPT_EUNSUPPORTED;                       // statistics / pooling exist only in the 16-byte epilogue
     if (const int rc = validate_operands(p)) return rc;
+    // ... and epilogue_scalar, where a launch lands when neither of the other two tiers takes it, has no code for them: it would
+    // leave col_sum / col_sqsum / pool_max untouched and report success (these launches run on 128 x 128 tiles: TI == 2; batched
+    // ones were refused above, so slice 0 decides)
+    if ((p.col_sum || p.pool_max) && !reg_epilogue_ok<2>(p, 0) && !vec_epilogue_ok(p, 0)) return PPT_EUNSUPPORTED;
     if (ppt_gemm256_dispatch(&p, 0, stream) == PPT_OK) return PPT_OK;     // the 256-row macro-tile core takes the big plain problems
     hipStream_t s = ppt_stream(stream);
     if (p.dtype == PPT_F32 && p.split16) {                                        // hi + lo half products (gemm_common.h, split16)

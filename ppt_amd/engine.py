@@ -596,7 +596,7 @@ def _sa_level(sd, branches, wc, npoint, xyz, feats, start, train, upd, xyz_first
                 y1, st1 = ops.conv12_stats(pts, w03, b0, sc0, sh0, w1c, sd[cb + "1.bias"])     # csrc/mpn1.hip: no tile staging
             else:
                 y1 = ops.gemm(None, w1c, out_dtype=T, a_mode=A_CONV1, pts=pts, w1=w03, b1=b0,
-                              a_scale=sc0, a_shift=sh0, bias=sd[cb + "1.bias"], col_stats=st1)
+                              a_scale=sc0, a_shift=sh0, bias=ops.aligned16(sd[cb + "1.bias"]), col_stats=st1)
         else:
             # layer 0 by linearity of the 1x1 conv: per source point P = W.[feat|xyz], per centre Q = b - W_xyz.c
             D = feats.shape[1]
@@ -615,7 +615,7 @@ def _sa_level(sd, branches, wc, npoint, xyz, feats, start, train, upd, xyz_first
             y0, part0 = ops.gather_add(P, Q, idx, N, T, want_stats=train)
             sc0, sh0 = _bn_affine(sd, bb + "0.", train, part0, 32, M, upd)
             y1 = ops.gemm(y0, wc.get(sd[cb + "1.weight"]), out_dtype=T, a_mode=A_AFFINE_RELU, a_scale=sc0, a_shift=sh0,
-                          bias=sd[cb + "1.bias"], col_stats=st1)
+                          bias=ops.aligned16(sd[cb + "1.bias"]), col_stats=st1)
         sc1, sh1 = _bn_affine(sd, bb + "1.", train, st1, 32, M, upd)
         C3 = c_out[i]
         pr = min(K, 64)
@@ -627,7 +627,7 @@ def _sa_level(sd, branches, wc, npoint, xyz, feats, start, train, upd, xyz_first
                 and (w2c.shape[1], C3, pr) in ops.AFFINE_CONV_POOL_SHAPES):
             ops.affine_conv_pool(y1, sc1, sh1, w2c, sd[cb + "2.bias"], pr, pmax, pmin, st2)      # csrc/affpool.hip: no tile staging
         else:
-            ops.gemm(y1, w2c, a_mode=A_AFFINE_RELU, a_scale=sc1, a_shift=sh1, bias=sd[cb + "2.bias"],
+            ops.gemm(y1, w2c, a_mode=A_AFFINE_RELU, a_scale=sc1, a_shift=sh1, bias=ops.aligned16(sd[cb + "2.bias"]),
                      want_out=False, pool_max=pmax, pool_min=pmin, pool_rows=pr, col_stats=st2)
         sc2, sh2 = _bn_affine(sd, bb + "2.", train, st2, 32, M, upd)
         ops.pool_finish(pmax, pmin, K // pr, sc2, sh2, out[:, col:col + C3])
@@ -666,17 +666,17 @@ def _pn2_tail(sd, p, wc, l2_xyz, l2, train, drop_masks, update_running):
     a[:, 3:3 + D] = l2
     cb, bb = p + "sa3.mlp_convs.", p + "sa3.mlp_bns."
     st = _stats_bufs(M, 256, dev, train)
-    y0 = ops.gemm(a, wc.get(sd[cb + "0.weight"], "w", pad_to=mult), out_dtype=T, bias=sd[cb + "0.bias"], col_stats=st)
+    y0 = ops.gemm(a, wc.get(sd[cb + "0.weight"], "w", pad_to=mult), out_dtype=T, bias=ops.aligned16(sd[cb + "0.bias"]), col_stats=st)
     sc, sh = _bn_affine(sd, bb + "0.", train, st, 32, M, update_running)
     st = _stats_bufs(M, 512, dev, train)
     y1 = ops.gemm(y0, wc.get(sd[cb + "1.weight"]), out_dtype=T, a_mode=A_AFFINE_RELU, a_scale=sc, a_shift=sh,
-                  bias=sd[cb + "1.bias"], col_stats=st)
+                  bias=ops.aligned16(sd[cb + "1.bias"]), col_stats=st)
     sc, sh = _bn_affine(sd, bb + "1.", train, st, 32, M, update_running)
     st = _stats_bufs(M, 1024, dev, train)
     pr = min(S2, 64)
     pmax = torch.empty((M // pr, 1024), dtype=torch.float32, device=dev)
     pmin = torch.empty_like(pmax)
-    ops.gemm(y1, wc.get(sd[cb + "2.weight"]), a_mode=A_AFFINE_RELU, a_scale=sc, a_shift=sh, bias=sd[cb + "2.bias"],
+    ops.gemm(y1, wc.get(sd[cb + "2.weight"]), a_mode=A_AFFINE_RELU, a_scale=sc, a_shift=sh, bias=ops.aligned16(sd[cb + "2.bias"]),
              want_out=False, pool_max=pmax, pool_min=pmin, pool_rows=pr, col_stats=st)
     sc, sh = _bn_affine(sd, bb + "2.", train, st, 32, M, update_running)
     x = torch.empty((B, 1024), dtype=T, device=dev)
@@ -684,7 +684,7 @@ def _pn2_tail(sd, p, wc, l2_xyz, l2, train, drop_masks, update_running):
     # FC head: Linear -> BatchNorm1d (over the batch) -> ReLU -> Dropout, twice (pointnet2.py:69-70)
     for fc, bn, width, mask in (("fc1.", "bn1.", 512, 0), ("fc2.", "bn2.", 256, 1)):
         st = _stats_bufs(B, width, dev, train)
-        h = ops.gemm(x, wc.get(sd[p + fc + "weight"]), out_dtype=torch.float32, bias=sd[p + fc + "bias"], col_stats=st)
+        h = ops.gemm(x, wc.get(sd[p + fc + "weight"]), out_dtype=torch.float32, bias=ops.aligned16(sd[p + fc + "bias"]), col_stats=st)
         sc, sh = _bn_affine(sd, p + bn, train, st, 32, B, update_running)
         last = fc == "fc2."
         x = ops.bn_act_rows(h, sc, sh, torch.float32 if last else T, mask=drop_masks[mask] if drop_masks is not None else None)
@@ -832,7 +832,7 @@ def pointmlp_forward(sd, p, wc, pc, fps_starts, train, drop_masks, update_runnin
     for fc, bn, mask in (("0.", "1.", 0), ("4.", "5.", 1)):
         w = wc.get(sd[c + fc + "weight"])
         st = _stats_bufs(B, w.shape[0], dev, train)
-        h = ops.gemm(x, w, out_dtype=torch.float32, bias=sd[c + fc + "bias"], col_stats=st)
+        h = ops.gemm(x, w, out_dtype=torch.float32, bias=ops.aligned16(sd[c + fc + "bias"]), col_stats=st)
         sc, sh = _bn_affine(sd, c + bn, train, st, 32, B, upd)
         last = fc == "4."
         x = ops.bn_act_rows(h, sc, sh, torch.float32 if last else T, mask=drop_masks[mask] if drop_masks is not None else None)

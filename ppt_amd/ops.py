@@ -97,6 +97,12 @@ def _chk(t, dtype=None, name="tensor"):
         raise RuntimeError(f"{name}: expected {dtype}, got {t.dtype}")
 
 
+def aligned16(t):
+    """t, or a copy of it at a 16-byte aligned address: ppt_gemm refuses statistics / pooling launches whose bias or group_add is
+    not (struct ppt_gemm_params), and a state-dict tensor can be a view at any element of a flat buffer"""
+    return t if t is None or t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 # ---------------------------------------------------------------------------------------------
 def fps(xyz, M, start):
     """H1.  xyz [B,N,3] f32, start [B] i64 -> (idx [B,M] i64, center [B,M,3] f32)."""
