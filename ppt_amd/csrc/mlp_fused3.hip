@@ -43,7 +43,10 @@ constexpr int W1_BYTES = HID * D * 2, W2_BYTES = D * HID * 2;
 
 // GELU (exact-erf form as an odd polynomial, ppt_act.h) with the saturation folded into a clamp of the erf argument: the
 // polynomial was fitted on |x| < 4 and erf(4 / sqrt 2) = 0.99994, so clamping x to [-4, 4] for the erf factor replaces gelu_poly's
-// compare + copysign + select by one v_med3_f32 (|difference| <= 6.3e-5 * |x| / 2 beyond 4: inside the polynomial's own error).
+// compare + copysign + select by one v_med3_f32.  Beyond 4 the factor stays 4 P(16) = 1 - 1.066e-4 (1 - erf(4 / sqrt 2) = 6.3e-5 AND
+// the fit's own 4.3e-5 at the end of its interval) while erf goes on to 1: |error| <= 1.07e-4 * |x| / 2 there -- 2.1e-4 at 4, 5.4e-4 at
+// 10, i.e. ABOVE gelu_poly's 2e-4: for x > 4 that is 5.4e-5 relative to the output, 1/70 of a bf16 ulp; for x < -4 the output is
+// -5.4e-5 |x| where GELU is 0 (tests/test_vit_block_ref_cpu.py measures both).
 // hs = 0.5 * (the row's DropPath factor): the factor rides on the GELU output for free, (rs * U) W2 = rs * (U W2)
 __device__ __forceinline__ float gelu_poly3(float x, float hs)
 {

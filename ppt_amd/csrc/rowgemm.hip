@@ -21,7 +21,8 @@
 // same bits), and (x - mean) * rstd * gamma + beta goes to LDS as bf16 -- the LayerNorm output never exists in HBM.
 // Column groups recompute it (3x for qkv, 4x for fc1): 1.5 KB per row out of L2 against 23 ... 31 GFLOP per launch.
 //
-// Epilogues: bias; GELU (erf, A&S 7.1.26 as gemm.hip) / QuickGELU with an optional copy of the pre-activation; or the
+// Epilogues: bias; GELU (gelu_poly of ppt_act.h: the exact-erf form as an odd polynomial, |error| <= 2e-4) / QuickGELU with an
+// optional copy of the pre-activation; or the
 // residual form out = residual + row_scale[m / rows] * (acc + bias) (+ residual2), fp32, in place allowed.
 #include "ppt_common.h"
 #include "ppt_act.h"
