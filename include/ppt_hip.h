@@ -53,7 +53,7 @@ const char *ppt_strerror(int code);
  *    ppt_nearest_rows_f32 / ppt_nearest_rows_workspace_bytes (csrc/nearest.hip);
  *    ppt_partseg_predict / ppt_render_balls / ppt_render_balls_workspace_bytes (csrc/render.hip);
  *    ppt_attention_ragged_fwd (csrc/attention_ragged.hip); ppt_sentence_rows / ppt_template_ensemble / ppt_cosine_head
- *    (csrc/zeroshot.hip).
+ *    (csrc/zeroshot.hip); ppt_ball_query_lt_f32 / ppt_pool_res_finish / ppt_cloud_height_f32 (csrc/pointnext.hip).
  * 6: ppt_gemm_params.split16 / split_a_pow2 / split_b_pow2 (new trailing fields: fp32 operands as hi + lo half pairs),
  *    ppt_attention_fwd_split16 / ppt_attention_bwd_split16 (new), ppt_pointmlp_cloud_rstd / ppt_pointmlp_pq (new).
  * 5: ppt_labels_check (new), ppt_gemm256 (new: the 256-row macro-tile GEMM core), ppt_set_gemm256 / ppt_get_gemm256 (new),
@@ -665,6 +665,7 @@ int ppt_sum_groups(const float *x, int64_t G, int k, int C, float *out, void *st
  * A 1x1 convolution over gathered neighbours is linear, so the first layer of a grouped MLP is evaluated per
  * SOURCE point (P = W.[feat|xyz], a small GEMM) and per centre (Q = b - W_xyz.centre) and then gathered:
  *   y[b,s,k,:] = P[b, idx[b,s,k], :] + Q[b,s,:]      (ppt_gather_add; also emits the 32-row (sum, M2) BN partials)
+ *   (P f32; y f32, bf16 or IEEE half: the fp32 sum rounded once; the partials are those of the un-rounded rows)
  * instead of gathering 323-wide inputs and multiplying K times more rows.
  * pool_finish: out[g, c] = relu(scale[c] * (scale[c] >= 0 ? max : min)[g, c] + shift[c]) folded over `fold`
  *   consecutive pooled rows, written with leading dimension ld_out (concatenation of the MSG branches).
@@ -675,6 +676,23 @@ int ppt_pool_finish(const void *pmax, const void *pmin, int p_dtype, int G, int 
                     const float *shift, void *out, int out_dtype, int64_t ld_out, void *stream);
 int ppt_bn_act_rows(const float *x, int M, int C, const float *scale, const float *shift, const float *mask,
                     void *y, int y_dtype, void *stream);
+
+/* ---- PointNeXt-S (models/pointnext/PointNeXt/openpoints; csrc/pointnext.hip) -------------------------------------------------
+ * ball_query_lt: the ball query of openpoints' compiled extension (cpp/pointnet2_batch/src/ball_query_gpu.cu:15-51): first K
+ *   indices in ascending order with (dx*dx + dy*dy) + dz*dz < radius_sq -- strict, direct form, every operation rounded to fp32 --
+ *   padded with the first hit; all indices 0 when nothing hits.  xyz [B,N,3], center [B,S,3] -> idx [B,S,K] i64 and, unless NULL,
+ *   grouped_xyz [B,S,K,3] = xyz[idx] - center.  N <= 8192, K <= 64 (K may exceed N), any S >= 1.
+ * pool_res_finish: the end of a residual set-abstraction level (backbone/pointnext.py:166-168):
+ *   out[g, c] = relu((scale[c] * (scale[c] >= 0 ? max : min)[g, c] + shift[c]) + identity[g, c]), max / min folded over `fold`
+ *   consecutive rows of pmax / pmin [G * fold, C] f32; identity [G, C] f32 or NULL; out [G, C] in out_dtype.  Product and sums are
+ *   rounded separately (no fused multiply-add).
+ * cloud_height: data/dataset_3d.py:311-314 (use_height): pc [B,N,3] -> out [B,N,4] = (x, y, z, y - min over the cloud of y), the
+ *   minimum and the subtraction in fp32; out 16-byte aligned. */
+int ppt_ball_query_lt_f32(const float *xyz, const float *center, int B, int N, int S, float radius_sq, int K, int64_t *idx,
+                          float *grouped_xyz, void *stream);
+int ppt_pool_res_finish(const float *pmax, const float *pmin, int G, int fold, int C, const float *scale, const float *shift,
+                        const float *identity, void *out, int out_dtype, void *stream);
+int ppt_cloud_height_f32(const float *pc, int B, int N, float *out, void *stream);
 /* ---- the prompt side's serial steps as single kernels (csrc/optim.hip) ------------------------------------------------
  * adamw_step: one torch.optim.AdamW update (main_cls.py:58-60, 198; amsgrad off) of a tensor of n f32 values:
  *   p *= 1 - lr * weight_decay; exp_avg += (g - exp_avg)(1 - beta1); exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) g^2;

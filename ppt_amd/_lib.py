@@ -128,6 +128,9 @@ _SIGNATURES = {
     "ppt_pool_finish": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64,
                                 c_void_p]),
     "ppt_bn_act_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "ppt_ball_query_lt_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    "ppt_pool_res_finish": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "ppt_cloud_height_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "ppt_gemm": (c_int, [ctypes.POINTER(GemmParams), c_void_p]),
     "ppt_gemm256": (c_int, [ctypes.POINTER(GemmParams), c_void_p]),
     "ppt_three_nn_interp_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,

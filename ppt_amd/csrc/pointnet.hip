@@ -421,6 +421,8 @@ extern "C" int ppt_gather_add(const void *P, int p_dtype, const float *Q, const 
         hipLaunchKernelGGL((gather_add_kernel<float, float>), grid, dim3(128), 0, s, (const float *)P, Q, idx, Nsrc, S, K, C, M, (float *)y, part_sum, part_m2);
     else if (p_dtype == PPT_F32 && y_dtype == PPT_BF16)
         hipLaunchKernelGGL((gather_add_kernel<float, bf16_t>), grid, dim3(128), 0, s, (const float *)P, Q, idx, Nsrc, S, K, C, M, (bf16_t *)y, part_sum, part_m2);
+    else if (p_dtype == PPT_F32 && y_dtype == PPT_F16)
+        hipLaunchKernelGGL((gather_add_kernel<float, f16_t>), grid, dim3(128), 0, s, (const float *)P, Q, idx, Nsrc, S, K, C, M, (f16_t *)y, part_sum, part_m2);
     else
         return PPT_EUNSUPPORTED;
     PPT_CHECK_LAUNCH();

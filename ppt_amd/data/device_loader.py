@@ -76,6 +76,16 @@ def numpy_draws(rs, recipe, train, rows, npoints):
     return d
 
 
+def add_height(pc):
+    """data/dataset_3d.py:311-314 (`use_height`, what PointNeXt reads) on a batch: pc [B,n,3] f32 -> [B,n,4], column 3 = y minus the
+    cloud's smallest y, both in fp32.  A device batch takes one launch (ops.cloud_height); a host tensor the same two torch operations."""
+    if pc.is_cuda:
+        from .. import ops
+        return ops.cloud_height(pc.contiguous())
+    y = pc[:, :, 1:2]
+    return torch.cat([pc, y - y.min(dim=1, keepdim=True)[0]], dim=2)
+
+
 def _rows_of(a):
     return [np.asarray(x) for x in a] if isinstance(a, (list, tuple)) else None
 
@@ -176,7 +186,8 @@ class DeviceCloudSet:
 class DeviceBatchLoader:
     """Iterate a DeviceCloudSet in batches made on the device.  Yields device tensors with the shapes and dtypes the reference's
     default collate gives: (pc [B, npoints, 3] f32, target [B] i64) for "modelnet" / "scanobjectnn", (pc, cls [B, 1] i32,
-    seg [B, npoints] i64) for "shapenetpart" (seg already `.long()`, as main_partseg.py:207 makes it).
+    seg [B, npoints] i64) for "shapenetpart" (seg already `.long()`, as main_partseg.py:207 makes it).  use_height=True (the
+    reference's --use_height, what PointNeXt reads): pc is [B, npoints, 4], `add_height` applied to the finished cloud.
 
     Order: `epoch_indices` -- DistributedSampler(shuffle, seed, drop_last) for (rank, world_size); drop_last also drops an
     incomplete last batch, as DataLoader(drop_last=True) does.  set_epoch(e) as with the sampler.
@@ -186,7 +197,7 @@ class DeviceBatchLoader:
     No stream is created here: see DevicePrefetcher._stream for what a further stream does to the two-stream schedule."""
 
     def __init__(self, cloud_set, batch_size, npoints, recipe, train, shuffle=True, drop_last=False, seed=0, draws="device", rank=0,
-                 world_size=1, ahead=2):
+                 world_size=1, ahead=2, use_height=False):
         if recipe not in RECIPES:
             raise ValueError(f"recipe must be one of {RECIPES}, got {recipe!r}")
         if draws not in ("device", "numpy"):
@@ -198,6 +209,7 @@ class DeviceBatchLoader:
         self.set, self.batch_size, self.npoints, self.recipe, self.train = cloud_set, int(batch_size), int(npoints), recipe, bool(train)
         self.shuffle, self.drop_last, self.seed, self.draws = bool(shuffle), bool(drop_last), int(seed), draws
         self.rank, self.world_size, self.ahead, self.epoch = int(rank), int(world_size), int(ahead), 0
+        self.use_height = bool(use_height)     # pc [B, npoints, 4]: the height column, taken after augmentation and shuffle (dataset_3d.py:306-314)
         epoch_indices(1, rank=self.rank, world_size=self.world_size)          # validates rank / world_size
         rows = cloud_set.rows(np.arange(len(cloud_set)))
         if recipe == "shapenetpart":
@@ -273,8 +285,8 @@ class DeviceBatchLoader:
                              shift=d.get("shift"), perm=d.get("perm"), seg_src=s.seg if part else None)
         target = s.labels.index_select(0, item)
         if part:
-            return (out[0], target.to(torch.int32).view(-1, 1), out[1])
-        return (out, target)
+            return (add_height(out[0]) if self.use_height else out[0], target.to(torch.int32).view(-1, 1), out[1])
+        return (add_height(out) if self.use_height else out, target)
 
     def __iter__(self):
         from .. import graphs

@@ -840,6 +840,145 @@ def pointmlp_forward(sd, p, wc, pc, fps_starts, train, drop_masks, update_runnin
 
 
 # =================================================================================================
+# PointNeXt-S encoder (models/pointnext/pointnext-s.yaml; PointNeXt/openpoints/models/backbone/pointnext.py:81-170, 311-443,
+# layers/group.py:177-272, classification/cls_base.py:78-140)
+# =================================================================================================
+def _pointnext_radii(radius=0.15, scaling=1.5, levels=4):
+    """PointNextEncoder._to_full_list (pointnext.py:389-407): the radius grows by `scaling` after every strided stage, in Python floats."""
+    out = []
+    for _ in range(levels):
+        out.append(radius)
+        radius *= scaling
+    return out
+
+
+POINTNEXT_LEVELS = [(r, 32) for r in _pointnext_radii()]        # (radius, nsample) of stages 1-4, stride 2 each
+# The operand format of this encoder in the performance mode: IEEE half (PPT_POINTNEXT_F16=0: bf16).  Every coordinate difference is
+# formed in fp32 (_pointnext_level), what the 16-bit GEMMs read is features behind a BatchNorm + ReLU and raw conv outputs in front
+# of one: |values| of order 1-100 against half's 65 504.  Measured at 32 x 1024 (profiles/r21_pointnext.md): the same rate in both
+# formats (0.1-0.6 % apart) and 6-9 x less error against fp64 with half.
+POINTNEXT_F16 = os.environ.get("PPT_POINTNEXT_F16", "1") != "0"
+
+
+def pointnext_group(pc, levels=None):
+    """The part of the PointNeXt forward that depends on coordinates only: per strided stage FPS from index 0 (sampling_gpu.cu:100-216;
+    first maximum on ties) and the strict ball query of the new points in the old ones (ops.ball_query_lt).  pc [B,N,3] f32 ->
+    flat list, per stage (rows [B*S] i64 = flat row b * N + index of every sampled point, new_xyz [B,S,3], neighbour indices [B,S,K])."""
+    levels = POINTNEXT_LEVELS if levels is None else levels
+    B = pc.shape[0]
+    out, xyz = [], pc.contiguous()
+    start = torch.zeros((B,), dtype=torch.int64, device=pc.device)
+    for r, K in levels:
+        N = xyz.shape[1]
+        cidx, new_xyz = ops.fps(xyz, N // 2, start)
+        nidx = ops.ball_query_lt(xyz, new_xyz, r, K)
+        rows = (cidx + torch.arange(B, device=pc.device).view(B, 1) * N).view(-1)
+        out += [rows, new_xyz, nidx]
+        xyz = new_xyz
+    return out
+
+
+def _pointnext_level(sd, p, wc, r, xyz4, N, f, rows, new_xyz, nidx, train, upd):
+    """SetAbstraction.forward with stride 2 and use_res (pointnext.py:140-170): xyz4 [B*N, 4] f32 (column 3 ignored), f [B*N, C] (T)
+    -> (centres as [B*S, 4] f32 rows, features [B*S, 2C] (T)).
+
+    The first conv reads cat([dp / r, f_j]) with dp = x_j - c: linear, so it runs per SOURCE point and per centre,
+        P = W_f.f_j + (W_xyz / r).x_j,   Q = -(W_xyz / r).c,   y0[b,s,k] = P[idx[b,s,k]] + Q[b,s]   (ppt_gather_add),
+    with the 1 / r of normalize_dp folded into cached coordinate columns.  Both coordinate terms are fp32 GEMMs (K = 4) in every mode:
+    a difference of positions rounded to 16 bits would carry an error of 2^-9 / r."""
+    T = wc.dtype
+    dev = f.device
+    B, S, K = nidx.shape
+    C = f.shape[1]
+    M = B * S * K
+    w0 = sd[p + "convs.0.0.weight"]
+    rf = float(torch.tensor(r, dtype=torch.float32))
+
+    def wx(sign, w0=w0, rf=rf):
+        return _pad_cols(sign * w0.detach().reshape(w0.shape[0], -1)[:, :3].float() / rf, 4, torch.float32)
+    wxs = wc.derived(("pnext_wx", p), (w0,), lambda: wx(1.0))
+    wxn = wc.derived(("pnext_wx_neg", p), (w0,), lambda: wx(-1.0))
+    # the fp32 mode's coordinate GEMMs follow the model's split16 switch like all its GEMMs; a 16-bit mode's run on the fp32 MFMA
+    # whatever the process-wide switch says (it belongs to whichever model spoke last: eager and replayed forwards must not differ by it)
+    split = None if T == torch.float32 else False
+    Pf = ops.gemm(f, wc.get(w0, cols=(3, 3 + C)), out_dtype=torch.float32)
+    P = ops.gemm(xyz4, wxs, out_dtype=torch.float32, residual=Pf, split=split)
+    cx = _pad_cols(new_xyz.view(B * S, 3), 4, torch.float32)
+    Q = ops.gemm(cx, wxn, out_dtype=torch.float32, split=split)
+    y0, part0 = ops.gather_add(P, Q, nidx, N, T, want_stats=train)
+    sc0, sh0 = _bn_affine(sd, p + "convs.0.1.", train, part0, 32, M, upd)
+    # second conv: BN + ReLU of the first in its A-prologue; only the max / min over the 32 samples and the BN partials are written
+    w1 = wc.get(sd[p + "convs.1.0.weight"])
+    C2 = w1.shape[0]
+    pmax = torch.empty((B * S, C2), dtype=torch.float32, device=dev)
+    pmin = torch.empty_like(pmax)
+    st1 = _stats_bufs(M, C2, dev, train)
+    ops.gemm(y0, w1, a_mode=A_AFFINE_RELU, a_scale=sc0, a_shift=sh0, want_out=False, pool_max=pmax, pool_min=pmin, pool_rows=K,
+             col_stats=st1)
+    sc1, sh1 = _bn_affine(sd, p + "convs.1.1.", train, st1, 32, M, upd)
+    # identity = skipconv(f[:, idx]) (Conv1d with bias, no norm), then relu(max_k bn(conv) + identity)
+    ident = ops.gemm(torch.index_select(f, 0, rows), wc.get(sd[p + "skipconv.0.weight"]), out_dtype=torch.float32,
+                     bias=sd[p + "skipconv.0.bias"])
+    return cx, ops.pool_res_finish(pmax, pmin, 1, sc1, sh1, ident, T)
+
+
+def pointnext_forward(sd, p, wc, pc4, train, drop_masks, update_running=True, grouped=None):
+    """BaseCls.forward of PointNEXT() (cls_base.py:30-32, pointnext.py:434-443): pc4 [B,N,4] f32 = (x, y, z, height) -> [B,256] f32.
+    drop_masks = (m1 [B,512], m2 [B,256]) or None; grouped = pointnext_group(pc4[..., :3]) when the grouping stage already ran.
+    Every BatchNorm follows `train` (batch statistics + running-stat updates, or the running statistics)."""
+    T = wc.dtype
+    B, N, _ = pc4.shape
+    dev = pc4.device
+    upd = update_running
+    mult = 8 if T in ops.HALF else 4
+    if grouped is None:
+        grouped = pointnext_group(pc4[..., :3].contiguous())
+    e = p + "encoder.encoder."
+    # stage 0: Conv1d(4 -> 32) with bias on the input rows, no norm, no activation
+    xyz4 = pc4.reshape(B * N, 4)
+    f = ops.gemm(_pad_cols(xyz4, mult, T), wc.get(sd[e + "0.0.convs.0.0.weight"], "w", pad_to=mult), out_dtype=T,
+                 bias=sd[e + "0.0.convs.0.0.bias"])
+    for i, (r, _) in enumerate(POINTNEXT_LEVELS):
+        rows, new_xyz, nidx = grouped[3 * i:3 * i + 3]
+        xyz4, f = _pointnext_level(sd, f"{e}{i + 1}.0.", wc, r, xyz4, N, f, rows, new_xyz, nidx, train, upd)
+        N = new_xyz.shape[1]
+    # stage 5: GroupAll, channels = [absolute xyz | features], two conv + BN + ReLU, max over the N remaining points
+    q = e + "5.0."
+    M, D = B * N, f.shape[1]
+    a = torch.zeros((M, (D + 3 + mult - 1) // mult * mult), dtype=T, device=dev)
+    a[:, :3] = xyz4[:, :3]
+    a[:, 3:3 + D] = f
+    w0 = wc.get(sd[q + "convs.0.0.weight"], "w", pad_to=mult)
+    st = _stats_bufs(M, w0.shape[0], dev, train)
+    y0 = ops.gemm(a, w0, out_dtype=T, col_stats=st)
+    sc, sh = _bn_affine(sd, q + "convs.0.1.", train, st, 32, M, upd)
+    w1 = wc.get(sd[q + "convs.1.0.weight"])
+    st = _stats_bufs(M, w1.shape[0], dev, train)
+    pr = 64 if N % 64 == 0 else N if N in (16, 32) else 0
+    if pr:
+        pmax = torch.empty((M // pr, w1.shape[0]), dtype=torch.float32, device=dev)
+        pmin = torch.empty_like(pmax)
+        ops.gemm(y0, w1, a_mode=A_AFFINE_RELU, a_scale=sc, a_shift=sh, want_out=False, pool_max=pmax, pool_min=pmin, pool_rows=pr,
+                 col_stats=st)
+        fold = N // pr
+    else:
+        # the pooled epilogue takes groups of 16 / 32 / 64 rows only: any other count writes the conv output and is reduced from it
+        pmax = pmin = ops.gemm(y0, w1, out_dtype=torch.float32, a_mode=A_AFFINE_RELU, a_scale=sc, a_shift=sh, col_stats=st)
+        fold = N
+    sc, sh = _bn_affine(sd, q + "convs.1.1.", train, st, 32, M, upd)
+    x = ops.pool_res_finish(pmax, pmin, fold, sc, sh, None, T)
+    # ClsHead: Linear (no bias) -> BatchNorm1d over the batch -> ReLU -> Dropout(0.5), twice; num_classes = -1: no classifier layer
+    h_ = p + "prediction.head."
+    for j, mask in ((0, 0), (2, 1)):
+        w = wc.get(sd[f"{h_}{j}.0.weight"])
+        st = _stats_bufs(B, w.shape[0], dev, train)
+        h = ops.gemm(x, w, out_dtype=torch.float32, col_stats=st)
+        sc, sh = _bn_affine(sd, f"{h_}{j}.1.", train, st, 32, B, upd)
+        x = ops.bn_act_rows(h, sc, sh, torch.float32 if j == 2 else T, mask=drop_masks[mask] if drop_masks is not None else None)
+    return x
+
+
+# =================================================================================================
 # text branch (CLIP text transformer, ULIP_models.py:35-67, 203-222)
 # =================================================================================================
 # LayerNorm -> in_proj / c_fc as ONE kernel (csrc/rowgemm.hip): two nodes fewer per layer, but OFF by default -- the

@@ -973,6 +973,50 @@ def bn_act_rows(x, scale, shift, y_dtype, mask=None):
     return y
 
 
+def ball_query_lt(xyz, center, radius, K, want_grouped=False):
+    """The ball query of PointNeXt's compiled extension (ppt_ball_query_lt_f32): first K indices in ascending order with the
+    direct-form fp32 distance (dx*dx + dy*dy) + dz*dz < float32(radius) * float32(radius), padded with the first hit, all 0 when
+    nothing hits.  xyz [B,N,3], center [B,S,3] -> idx [B,S,K] i64 [, grouped_xyz [B,S,K,3] = xyz[idx] - center]."""
+    _chk(xyz, torch.float32, "xyz"); _chk(center, torch.float32, "center")
+    import numpy as np
+    B, N, _ = xyz.shape
+    S = center.shape[1]
+    idx = torch.empty((B, S, K), dtype=torch.int64, device=xyz.device)
+    g = torch.empty((B, S, K, 3), dtype=torch.float32, device=xyz.device) if want_grouped else None
+    r2 = float(np.float32(radius) * np.float32(radius))
+    if profiler is not None:
+        profiler.begin("ball_query", float(B) * (12 * N + 12 * S + 8 * S * K + (12 * S * K if want_grouped else 0)))
+    _lib.check(_lib.lib().ppt_ball_query_lt_f32(_p(xyz), _p(center), B, N, S, r2, K, _p(idx), _p(g), _stream()),
+               "ppt_ball_query_lt_f32")
+    if profiler is not None:
+        profiler.end()
+    return (idx, g) if want_grouped else idx
+
+
+def pool_res_finish(pmax, pmin, fold, scale, shift, identity, out_dtype):
+    """out[g] = relu((scale * (scale >= 0 ? max : min) + shift) + identity[g]) folded over `fold` pooled rows (ppt_pool_res_finish):
+    pmax / pmin [G * fold, C] f32, identity [G, C] f32 | None -> [G, C] in out_dtype."""
+    _chk(pmax, torch.float32, "pmax"); _chk(pmin, torch.float32, "pmin"); _chk(identity, torch.float32, "identity")
+    _chk(scale, torch.float32, "scale"); _chk(shift, torch.float32, "shift")
+    C = pmax.shape[1]
+    G = pmax.shape[0] // fold
+    assert pmax.shape[0] == G * fold and pmin.shape == pmax.shape and (identity is None or tuple(identity.shape) == (G, C))
+    out = torch.empty((G, C), dtype=out_dtype, device=pmax.device)
+    _lib.check(_lib.lib().ppt_pool_res_finish(_p(pmax), _p(pmin), G, fold, C, _p(scale), _p(shift), _p(identity), _p(out),
+                                              dtype_code(out), _stream()), "ppt_pool_res_finish")
+    return out
+
+
+def cloud_height(pc):
+    """data/dataset_3d.py:311-314 (use_height): pc [B,N,3] f32 -> [B,N,4] f32, column 3 = y - min over the cloud of y."""
+    _chk(pc, torch.float32, "pc")
+    B, N, C = pc.shape
+    assert C == 3
+    out = torch.empty((B, N, 4), dtype=torch.float32, device=pc.device)
+    _lib.check(_lib.lib().ppt_cloud_height_f32(_p(pc), B, N, _p(out), _stream()), "ppt_cloud_height_f32")
+    return out
+
+
 def gn_lrelu_max_forward(y, gamma, beta, groups, eps, slope):
     """y [B,Q,K,C] f32 -> (out [B,Q,C], arg [B,Q,C] i32, mean [B,G], rstd [B,G]): GroupNorm(groups) + LeakyReLU(slope) +
     max over K (DGCNN_Propagation, pointbert/pointnet2_utils.py:371-467)."""

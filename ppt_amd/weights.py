@@ -6,6 +6,7 @@ the product and the oracle side of every test -- and bench.py -- draw the SAME v
 generator: every tensor is seeded by crc32(key) and produced with numpy's PCG64, which is
 identical on every machine.  Keys and shapes are the reference's.
 """
+import re
 import zlib
 from collections import OrderedDict
 
@@ -176,6 +177,36 @@ def pointmlp_spec(prefix="point_encoder."):
     return s
 
 
+POINTNEXT = dict(width=32, in_channels=4, levels=4, head=(512, 256))   # models/pointnext/pointnext-s.yaml
+
+
+def pointnext_spec(prefix="point_encoder."):
+    """(key, shape) list of PointNEXT().state_dict() (models/pointnext/pointnext.py:18-29: BaseCls of pointnext-s.yaml;
+    backbone/pointnext.py:81-138, 335-387, classification/cls_base.py:104-127), in the reference's order."""
+    def bn(p, c):
+        return [(p + k, (c,)) for k in ("weight", "bias", "running_mean", "running_var")] + [(p + "num_batches_tracked", ())]
+    e = prefix + "encoder.encoder."
+    c = POINTNEXT["width"]
+    s = [(e + "0.0.convs.0.0.weight", (c, POINTNEXT["in_channels"], 1)), (e + "0.0.convs.0.0.bias", (c,))]
+    for i in range(1, POINTNEXT["levels"] + 1):
+        q = f"{e}{i}.0."
+        s += [(q + "skipconv.0.weight", (2 * c, c, 1)), (q + "skipconv.0.bias", (2 * c,))]
+        s += [(q + "convs.0.0.weight", (c, c + 3, 1, 1))] + bn(q + "convs.0.1.", c)
+        s += [(q + "convs.1.0.weight", (2 * c, c, 1, 1))] + bn(q + "convs.1.1.", 2 * c)
+        c *= 2
+    q = f"{e}{POINTNEXT['levels'] + 1}.0."
+    s += [(q + "convs.0.0.weight", (c, c + 3, 1, 1))] + bn(q + "convs.0.1.", c)
+    s += [(q + "convs.1.0.weight", (c, c, 1, 1))] + bn(q + "convs.1.1.", c)
+    for j, out in zip((0, 2), POINTNEXT["head"]):
+        s += [(f"{prefix}prediction.head.{j}.0.weight", (out, c))] + bn(f"{prefix}prediction.head.{j}.1.", out)
+        c = out
+    return s
+
+
+def ulip_pn_next_state_dict(seed=0, with_token_embedding=False, as_torch=True):
+    return synth_state_dict(ulip_spec(256, with_token_embedding) + pointnext_spec(), seed, as_torch)
+
+
 def ulip_pn_mlp_state_dict(seed=0, with_token_embedding=False, as_torch=True):
     return synth_state_dict(ulip_spec(256, with_token_embedding) + pointmlp_spec(), seed, as_torch)
 
@@ -186,6 +217,9 @@ def ulip_pn2_ssg_state_dict(seed=0, with_token_embedding=False, as_torch=True):
 
 def ulip_pn2_msg_state_dict(seed=0, with_token_embedding=False, as_torch=True):
     return synth_state_dict(ulip_spec(256, with_token_embedding) + pointnet2_msg_spec(), seed, as_torch)
+
+
+_POINTNEXT_KEY = re.compile(r"encoder\.encoder\.\d+\.0\.|prediction\.head\.\d+\.")
 
 
 def _rng(key, seed):
@@ -214,6 +248,8 @@ def synth_tensor(key, shape, seed=0):
         or any(t in key for t in (".norm1.", ".norm2.", ".norm.", ".ln_1.", ".ln_2.", "ln_final.",
                                      "first_conv.1.", "second_conv.1.", "mlp_bns", ".bn", "bn_blocks",
                                      "layer1.1.", "layer2.1."))
+    if _POINTNEXT_KEY.search(key):          # PointNeXt: the norm of a block is its module 1
+        is_norm = key.rsplit(".", 2)[-2] == "1"
     if is_norm and leaf == "weight":
         return (1.0 + 0.1 * r.standard_normal(shape)).astype(np.float32)
     if leaf in ("bias", "in_proj_bias"):
