@@ -53,7 +53,8 @@ const char *ppt_strerror(int code);
  *    ppt_nearest_rows_f32 / ppt_nearest_rows_workspace_bytes (csrc/nearest.hip);
  *    ppt_partseg_predict / ppt_render_balls / ppt_render_balls_workspace_bytes (csrc/render.hip);
  *    ppt_attention_ragged_fwd (csrc/attention_ragged.hip); ppt_sentence_rows / ppt_template_ensemble / ppt_cosine_head
- *    (csrc/zeroshot.hip); ppt_ball_query_lt_f32 / ppt_pool_res_finish / ppt_cloud_height_f32 (csrc/pointnext.hip).
+ *    (csrc/zeroshot.hip); ppt_ball_query_lt_f32 / ppt_pool_res_finish / ppt_cloud_height_f32 (csrc/pointnext.hip);
+ *    ppt_cloud_augment_f32 / ppt_cloud_draws_aug (csrc/cloud_augment.hip).
  * 6: ppt_gemm_params.split16 / split_a_pow2 / split_b_pow2 (new trailing fields: fp32 operands as hi + lo half pairs),
  *    ppt_attention_fwd_split16 / ppt_attention_bwd_split16 (new), ppt_pointmlp_cloud_rstd / ppt_pointmlp_pq (new).
  * 5: ppt_labels_check (new), ppt_gemm256 (new: the 256-row macro-tile GEMM core), ppt_set_gemm256 / ppt_get_gemm256 (new),
@@ -791,6 +792,59 @@ int ppt_cloud_prep_f32(const float *src, int M, int Nmax, int C, const int32_t *
 int ppt_cloud_draws(const int64_t *index, int B, const int32_t *rows, int rows_all, int n, uint64_t seed, uint32_t epoch,
                     int64_t *start, double *scale, double *shift, int32_t *perm, int64_t *sel, const uint32_t *raw_ctr,
                     int raw_count, uint32_t *raw_out, void *stream);
+/* The reference's augmentations (data/dataset_3d.py:63-153, what ShapeNet.__getitem__ :590-595 chains) on a finished batch
+ * pc [B, n, 3] f32 -- what ppt_cloud_prep_f32 returns (csrc/cloud_augment.hip).  One workgroup per cloud, the cloud in LDS
+ * (n <= 8192), `count` <= PPT_AUG_MAX_STAGES stages applied in the order given, one pass and one barrier each, one store:
+ * out [B, n, 3] f32, or [B, n, 4] when PPT_AUG_HEIGHT closes the list; out 16-byte aligned.  Per stage (a, b: device arrays):
+ *   PPT_AUG_DROPOUT  a = mask [B, n] u8     row i <- row 0 where mask[b, i] != 0 (row 0 as it is at this stage)
+ *   PPT_AUG_SCALE    a = s [B] f64          (float)((double)v * s[b])
+ *   PPT_AUG_SHIFT    a = t [B, 3] f64       (float)((double)v + t[b, c])
+ *   PPT_AUG_ROTATE   a = R [B, 3, 3] f64    out[c] = (float)(((double)x * R[0][c] + (double)y * R[1][c]) + (double)z * R[2][c]): the row
+ *                                           vector times R, each product and sum rounded in f64, nothing fused, one rounding to f32
+ *                                           (np.dot(pc, R) stored into a float32 array).  Two rotations are two stages: the
+ *                                           reference rounds to f32 between them.
+ *   PPT_AUG_JITTER   a = noise [B, n, 3] f64, already clip(sigma * randn):  (float)(noise + (double)v)
+ *   PPT_AUG_AFFINE   a = scale, b = shift [B, 3] f64:  (float)((double)v * scale[b, c] + shift[b, c]), translate_pointcloud
+ *   PPT_AUG_HEIGHT   no parameters; the last stage only: column 3 = y - min_i y in f32, as ppt_cloud_height_f32
+ * Every rounding is numpy's (>= 2), so the output is bit-identical given the same parameters.  PPT_EINVAL: a NULL pointer, n <= 0,
+ * count outside [1, 8], an unknown kind, HEIGHT anywhere but last, a misaligned out (16) or f64 array (8); PPT_EUNSUPPORTED:
+ * n > 8192.  Nothing is launched in either case.  No parameter is used as an index: a mask or matrix with arbitrary contents gives
+ * wrong values, never an access outside the arrays. */
+#define PPT_AUG_DROPOUT 1
+#define PPT_AUG_SCALE 2
+#define PPT_AUG_SHIFT 3
+#define PPT_AUG_ROTATE 4
+#define PPT_AUG_JITTER 5
+#define PPT_AUG_AFFINE 6
+#define PPT_AUG_HEIGHT 7
+#define PPT_AUG_MAX_STAGES 8
+typedef struct ppt_aug_stage {
+    int kind;
+    const void *a, *b;
+} ppt_aug_stage;
+int ppt_cloud_augment_f32(const float *pc, int B, int n, const ppt_aug_stage *stages, int count, float *out, void *stream);
+/* The draws of those stages from the generator of ppt_cloud_draws: Philox4x32-10, counter = (index[b], epoch, slot, block),
+ * key = seed; u(hi, lo) = the 53-bit uniform in [0, 1) of two words, as in ppt_cloud_draws.  Slots 0-3 belong to ppt_cloud_draws and
+ * are untouched.  Every output is optional (NULL = not drawn), all f64 but the mask:
+ *   slot 4  ratio [B]        = u(w0, w1) * max_dropout of block 0                                     (np.random.random() * 0.875)
+ *   slot 5  mask [B, n] u8   block j: row 2j <- u(w0, w1) <= ratio, row 2j + 1 <- u(w2, w3) <= ratio  (ratio is a by-product of mask)
+ *   slot 6  scale [B]        = scale_low + (scale_high - scale_low) * u(w0, w1) of block 0            (uniform(0.8, 1.25))
+ *   slot 7  shift [B, 3]     axis c = -shift_range + (shift_range - -shift_range) * u(w0, w1) of block c   (uniform(-0.1, 0.1))
+ *   slot 8  angles [B, 3]    = clip(angle_sigma * z, +-angle_clip): block 0 gives z for angles 0 and 1, block 1's first z angle 2;
+ *           perturb [B,3,3]  = Rz (Ry Rx) of those angles (dataset_3d.py:141-150), formed in f64, every sum of three products left
+ *                              to right and unfused (angles is a by-product of perturb)
+ *   slot 9  angle [B]        = u(w0, w1) * 2 pi of block 0;  rotate [B, 3, 3] = [[c, 0, s], [0, 1, 0], [-s, 0, c]]   (:73-78)
+ *   slot 10 noise [B, n, 3]  flat element 2j <- z0, 2j + 1 <- z1 of block j, each clip(jitter_sigma * z, +-jitter_clip)
+ * Normals are Box-Muller in f64 on one block: u1 = u(w0, w1), u2 = u(w2, w3), r = sqrt(-2 log(1 - u1)) (the argument is in (0, 1]),
+ * z0 = r cos(2 pi u2), z1 = r sin(2 pi u2).  log / sin / cos are the device library's (within a few ulp of numpy's).
+ * magnitudes: host array of PPT_AUG_MAGNITUDES doubles {max_dropout, scale_low, scale_high, shift_range, angle_sigma, angle_clip,
+ * jitter_sigma, jitter_clip}, or NULL for the reference's {0.875, 0.8, 1.25, 0.1, 0.06, 0.18, 0.01, 0.05}.
+ * PPT_EINVAL: NULL index, B or n <= 0, nothing asked for, a by-product without its draw, a non-finite magnitude;
+ * PPT_EUNSUPPORTED: n > 8192. */
+#define PPT_AUG_MAGNITUDES 8
+int ppt_cloud_draws_aug(const int64_t *index, int B, int n, uint64_t seed, uint32_t epoch, const double *magnitudes, double *ratio,
+                        uint8_t *mask, double *scale, double *shift, double *angles, double *perturb, double *angle, double *rotate,
+                        double *noise, void *stream);
 
 /* ---- validation metrics (ABI 7, additive; csrc/metrics.hip; host side: ppt_amd/evaluate.py) ---------------------------------
  * What the reference's validate() loops take out of a batch of logits, as one launch per batch and one small record per sample;

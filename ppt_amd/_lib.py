@@ -97,6 +97,11 @@ class WprepItem(ctypes.Structure):
                 ("out", c_void_p), ("out_t", c_void_p)]
 
 
+class AugStage(ctypes.Structure):
+    """struct ppt_aug_stage (include/ppt_hip.h) -- field order must match the header."""
+    _fields_ = [("kind", c_int), ("a", c_void_p), ("b", c_void_p)]
+
+
 class RowGemmParams(ctypes.Structure):
     """struct ppt_rowgemm_params (include/ppt_hip.h) -- field order must match the header."""
     _fields_ = [
@@ -244,6 +249,9 @@ _SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ppt_cloud_draws": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "ppt_cloud_augment_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "ppt_cloud_draws_aug": (c_int, [c_void_p, c_int, c_int, ctypes.c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ppt_cls_metrics": (c_int, [c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p]),
     "ppt_partseg_metrics_chunks": (c_int, [c_int]),
     "ppt_partseg_metrics": (c_int, [c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,

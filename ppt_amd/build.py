@@ -25,6 +25,7 @@ COMMON = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-
 PER_FILE = {"fps.hip": ["-ffp-contract=off"], "knn_group.hip": ["-ffp-contract=off"],
             # the input pipeline reproduces numpy bit for bit: no contraction, IEEE-rounded fp32 `/` and sqrtf (hipcc's default, pinned)
             "cloud_prep.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+            "cloud_augment.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
             # the renderer's pixel values are a stated sequence of double operations: no fused multiply-add
             "render.hip": ["-ffp-contract=off"],
             # the strict ball query and the height column are index- / bit-exact against uncontracted fp32 restatements

@@ -7,10 +7,14 @@ What the reference's datasets do per sample, every epoch, in DataLoader workers 
     ScanObjectNN (:406-419)             the first num_points rows (no normalisation), and for the train split translate + shuffle
     ShapeNetPart (:734-757)             pc_normalize, then np.random.choice(len, npoints, replace=True) rows of the cloud and of its
                                         per-point part labels
+    ShapeNet (:576-607)                 farthest point sampling N -> npoints (or, for a cloud of npoints rows, a shuffle of its rows),
+                                        pc_norm, then random_point_dropout, random_scale_point_cloud, shift_point_cloud,
+                                        rotate_perturbation_point_cloud, rotate_point_cloud (recipe "shapenet55"; what
+                                        data/ShapeNet-55.yaml configures)
 
 ModelNet40 at 8192 points is under 1 GB; the raw clouds simply stay in device memory (`DeviceCloudSet`).  `DeviceBatchLoader` then
-produces a batch with one batched launch of the path's FPS kernel (csrc/fps.hip) and one launch of csrc/cloud_prep.hip for
-everything after it -- no workers, no pickling, no host copy of a cloud -- `ahead` batches in front of the consumer on the grouping
+produces a batch with one batched launch of the path's FPS kernel (csrc/fps.hip), one launch of csrc/cloud_prep.hip for
+everything after it and, where augmentations are asked for, one launch of csrc/cloud_augment.hip -- no workers, no pickling, no host copy of a cloud -- `ahead` batches in front of the consumer on the grouping
 stream (graphs.shared_group_stream), each yielded tensor carrying its completion event like a DevicePrefetcher batch.
 
 The random draws come from one of two places:
@@ -23,6 +27,19 @@ The random draws come from one of two places:
     draws="device"  csrc/cloud_prep.hip: ppt_cloud_draws, Philox4x32-10 keyed by `seed` with the counter (dataset index, epoch, draw,
                     block): a sample's draws do not depend on the batch size, the number of ranks or the batch it lands in, and
                     the launching thread does no per-sample work.
+
+Augmentations (ppt_amd/data/augment.py; csrc/cloud_augment.hip).  `augment=` takes a tuple of stage names out of ("dropout", "scale",
+"shift", "rotate_perturbation", "rotate", "jitter") and is valid with every recipe: the stages are applied to the recipe's finished
+cloud (after its own translate and shuffle, before the height column) as if the reference functions were called on pc[None] in that
+order, and their draws follow the recipe's own draws in that order -- in numpy mode from the same generator (dropout: random(),
+random(npoints); scale: uniform(0.8, 1.25, 1); shift: uniform(-0.1, 0.1, (1, 3)); rotate_perturbation: randn(3); rotate: uniform();
+jitter: randn(1, npoints, 3)), in device mode from ppt_cloud_draws_aug (slots 4-10 of the same counter).  Recipe "shapenet55" with
+train=True chains the first five itself (ShapeNet.__getitem__ always augments; here the test split takes the normalised sample as
+it is) and yields (pc, target).  Its row selection: FPS from a fresh randint(0, rows) start when the cloud has more rows than
+npoints; otherwise the reference's random_sample, which shuffles ONE persistent arange(npoints) cumulatively -- in numpy mode the
+loader owns that array for its lifetime, as the reference's dataset object does; in device mode every (index, epoch) gets a fresh
+Philox permutation instead (a uniformly random order either way; the cumulative state is what a worker process would not share).
+Not covered: the rendered images, the captions and their random.choice, normals, clouds of differing length under FPS.
 """
 import collections
 import math
@@ -30,7 +47,11 @@ import math
 import numpy as np
 import torch
 
-RECIPES = ("modelnet", "scanobjectnn", "shapenetpart")
+from .augment import KERNEL_STAGE, SHAPENET_CHAIN, check_stages, host_stage_draws, kernel_stage
+
+RECIPES = ("modelnet", "scanobjectnn", "shapenetpart", "shapenet55")
+FPS_RECIPES = ("modelnet", "shapenet55")
+KERNEL_PARAMS = {key for _, key in KERNEL_STAGE.values()}      # mask, scale, shift, perturb, rotate, noise: the draws a stage reads
 MAX_ROWS = 16384          # csrc/fps.hip: N <= 16384
 MAX_NPOINTS = 8192        # csrc/cloud_prep.hip: one cloud of the batch in LDS
 
@@ -60,19 +81,39 @@ def epoch_indices(n_items, epoch=0, shuffle=True, seed=0, drop_last=False, rank=
     return np.asarray(idx[rank:total:world_size], dtype=np.int64)
 
 
-def numpy_draws(rs, recipe, train, rows, npoints):
+def numpy_draws(rs, recipe, train, rows, npoints, augment=(), permutation=None):
     """One sample's draws from the np.random.RandomState `rs`, in the order the reference's __getitem__ makes them.  -> dict with
-    the ones this recipe / split needs of start (int), scale [3] f64, shift [3] f64, perm [npoints], sel [npoints]."""
+    the ones this recipe / split needs of start (int), scale [3] f64, shift [3] f64, perm [npoints], sel [npoints].
+    "shapenet55" (ShapeNet.__getitem__, :581-595): randint(0, rows) when npoints < rows, otherwise a shuffle of `permutation` (the
+    dataset's persistent arange(npoints), :545 / :572, changed in place; None: a fresh one) whose head is `sel`; then for the train
+    split random(), random(npoints), uniform(0.8, 1.25, 1), uniform(-0.1, 0.1, (1, 3)), randn(3), uniform().
+    augment: stage names (ppt_amd.data.augment.STAGES) whose draws follow, as the reference function of each makes them for pc[None].
+    Augmentation draws are keyed aug_ratio, aug_u [npoints], aug_mask [npoints] u8, aug_scale (a number), aug_shift [3], aug_angles [3],
+    aug_perturb [3, 3], aug_angle (a number), aug_rotate [3, 3], aug_noise [npoints, 3]."""
     d = {}
+    stages = tuple(augment)
     if recipe == "shapenetpart":
         d["sel"] = rs.choice(rows, npoints, replace=True)                     # dataset_3d.py:752
-        return d
-    if recipe == "modelnet" and npoints < rows:
-        d["start"] = rs.randint(0, rows)                                      # :50, inside farthest_point_sample
-    if train:
-        d["scale"] = rs.uniform(low=2. / 3., high=3. / 2., size=[3])          # :156
-        d["shift"] = rs.uniform(low=-0.2, high=0.2, size=[3])                 # :157
-        d["perm"] = rs.permutation(npoints)                                   # np.random.shuffle(cloud): the same swaps, applied to arange
+    elif recipe == "shapenet55":
+        if npoints < rows:
+            d["start"] = rs.randint(0, rows)                                  # :50, inside farthest_point_sample
+        else:
+            if permutation is None:
+                permutation = np.arange(npoints)
+            rs.shuffle(permutation)                                           # :572
+            d["sel"] = permutation[:npoints].copy()
+        if train:
+            stages = SHAPENET_CHAIN + stages
+    else:
+        if recipe == "modelnet" and npoints < rows:
+            d["start"] = rs.randint(0, rows)                                  # :50, inside farthest_point_sample
+        if train:
+            d["scale"] = rs.uniform(low=2. / 3., high=3. / 2., size=[3])      # :156
+            d["shift"] = rs.uniform(low=-0.2, high=0.2, size=[3])             # :157
+            d["perm"] = rs.permutation(npoints)                               # np.random.shuffle(cloud): the same swaps, applied to arange
+    for stage in stages:
+        for k, v in host_stage_draws(rs, stage, 1, npoints).items():
+            d["aug_" + k] = v[0]
     return d
 
 
@@ -188,6 +229,8 @@ class DeviceBatchLoader:
     default collate gives: (pc [B, npoints, 3] f32, target [B] i64) for "modelnet" / "scanobjectnn", (pc, cls [B, 1] i32,
     seg [B, npoints] i64) for "shapenetpart" (seg already `.long()`, as main_partseg.py:207 makes it).  use_height=True (the
     reference's --use_height, what PointNeXt reads): pc is [B, npoints, 4], `add_height` applied to the finished cloud.
+    Recipe "shapenet55" yields (pc, target) and, for train=True, carries ShapeNet's five augmentations; augment=(stage names) adds
+    augmentations to any recipe (the module text says how); with either, the height column comes out of the augmentation launch.
 
     Order: `epoch_indices` -- DistributedSampler(shuffle, seed, drop_last) for (rank, world_size); drop_last also drops an
     incomplete last batch, as DataLoader(drop_last=True) does.  set_epoch(e) as with the sampler.
@@ -197,7 +240,7 @@ class DeviceBatchLoader:
     No stream is created here: see DevicePrefetcher._stream for what a further stream does to the two-stream schedule."""
 
     def __init__(self, cloud_set, batch_size, npoints, recipe, train, shuffle=True, drop_last=False, seed=0, draws="device", rank=0,
-                 world_size=1, ahead=2, use_height=False):
+                 world_size=1, ahead=2, use_height=False, augment=None):
         if recipe not in RECIPES:
             raise ValueError(f"recipe must be one of {RECIPES}, got {recipe!r}")
         if draws not in ("device", "numpy"):
@@ -210,6 +253,12 @@ class DeviceBatchLoader:
         self.shuffle, self.drop_last, self.seed, self.draws = bool(shuffle), bool(drop_last), int(seed), draws
         self.rank, self.world_size, self.ahead, self.epoch = int(rank), int(world_size), int(ahead), 0
         self.use_height = bool(use_height)     # pc [B, npoints, 4]: the height column, taken after augmentation and shuffle (dataset_3d.py:306-314)
+        self.augment = () if augment is None else check_stages(augment)
+        own = SHAPENET_CHAIN if recipe == "shapenet55" and self.train else ()
+        self._aug_stages = check_stages(own + self.augment, f"recipe {recipe!r} with augment")      # () = today's launches, nothing more
+        if len(self._aug_stages) + self.use_height > 8:
+            raise ValueError("at most 8 augmentation stages in one launch, the height column included")
+        self._permutation = np.arange(self.npoints)      # "shapenet55", numpy draws: ShapeNet.permutation (:545), shuffled cumulatively
         epoch_indices(1, rank=self.rank, world_size=self.world_size)          # validates rank / world_size
         rows = cloud_set.rows(np.arange(len(cloud_set)))
         if recipe == "shapenetpart":
@@ -218,10 +267,10 @@ class DeviceBatchLoader:
         else:
             if rows.min() < self.npoints:
                 raise ValueError(f"recipe {recipe!r}: every cloud needs at least npoints = {self.npoints} rows (shortest: {rows.min()})")
-            if recipe == "modelnet" and rows.min() != rows.max():
-                raise ValueError("recipe 'modelnet': the batched FPS launch walks one row count for all its clouds; give clouds of one "
+            if recipe in FPS_RECIPES and rows.min() != rows.max():
+                raise ValueError(f"recipe {recipe!r}: the batched FPS launch walks one row count for all its clouds; give clouds of one "
                                  "length (ModelNet's are), e.g. one DeviceCloudSet per length")
-        self._fps_rows = int(rows[0]) if recipe == "modelnet" and rows[0] > self.npoints else 0
+        self._fps_rows = int(rows[0]) if recipe in FPS_RECIPES and rows[0] > self.npoints else 0
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -234,12 +283,33 @@ class DeviceBatchLoader:
         n = len(epoch_indices(len(self.set), 0, False, 0, self.drop_last, self.rank, self.world_size))
         return n // self.batch_size if self.drop_last else math.ceil(n / self.batch_size)
 
+    def _recipe_draws(self):
+        """which of ppt_cloud_draws' outputs the recipe itself needs"""
+        part, sn = self.recipe == "shapenetpart", self.recipe == "shapenet55"
+        translate = self.train and self.recipe in ("modelnet", "scanobjectnn")
+        return dict(start=self._fps_rows > 0, affine=translate, perm=translate or (sn and not self._fps_rows), sel=part)
+
+    def plan(self):
+        """The launches one batch takes, in order (names of ppt_amd.ops functions); numpy draws add one host-to-device copy instead
+        of the draw launches."""
+        p = []
+        if self.draws == "device":
+            p += ["cloud_draws"] if any(self._recipe_draws().values()) else []
+            p += ["cloud_draws_aug"] if self._aug_stages else []
+        p += ["fps"] if self._fps_rows else []
+        p.append("cloud_prep")
+        if self._aug_stages:
+            p.append("cloud_augment")     # the height column, if any, is its last stage
+        elif self.use_height:
+            p.append("cloud_height")
+        return tuple(p)
+
     # ---- one batch, queued on the current (= the grouping) stream ------------------------------------------------------------
     def _host_draws(self, rs, idx):
         """numpy mode: the batch's draws in ONE pinned buffer (a single asynchronous copy), viewed per array on the device."""
         B, n = len(idx), self.npoints
         rows = self.set.rows(idx)
-        per = [numpy_draws(rs, self.recipe, self.train, int(r), n) for r in rows]
+        per = [numpy_draws(rs, self.recipe, self.train, int(r), n, self.augment, self._permutation) for r in rows]
         parts = {}
         if "start" in per[0]:
             parts["start"] = np.asarray([d["start"] for d in per], dtype=np.int64)
@@ -248,8 +318,13 @@ class DeviceBatchLoader:
             parts["shift"] = np.stack([d["shift"] for d in per]).astype(np.float64)
         if "sel" in per[0]:
             parts["sel"] = np.stack([d["sel"] for d in per]).astype(np.int64)
+        for k in per[0]:
+            if k.startswith("aug_") and k[4:] in KERNEL_PARAMS:                            # what the kernel reads: f64, but for the mask
+                parts[k] = np.stack([np.asarray(d[k]) for d in per])
         if "perm" in per[0]:
-            parts["perm"] = np.stack([d["perm"] for d in per]).astype(np.int32)            # last: the only 4-byte array
+            parts["perm"] = np.stack([d["perm"] for d in per]).astype(np.int32)            # after the 8-byte arrays: 4-byte items
+        if "aug_mask" in parts:
+            parts["aug_mask"] = parts.pop("aug_mask")                                      # last: single bytes
         if not parts:
             return {}
         total = sum(a.nbytes for a in parts.values())
@@ -260,30 +335,41 @@ class DeviceBatchLoader:
             spans[k] = (off, a.nbytes, a.shape, a.dtype)
             off += a.nbytes
         dev = pin.to(self.set.device, non_blocking=True)
-        tdt = {np.dtype(np.int64): torch.int64, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32}
+        tdt = {np.dtype(np.int64): torch.int64, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32,
+               np.dtype(np.uint8): torch.uint8}
         return {k: dev[o:o + nb].view(tdt[np.dtype(dt)]).view(*shape) for k, (o, nb, shape, dt) in spans.items()}
 
     def _produce(self, item, idx, rs):
         from .. import ops
         s, n = self.set, self.npoints
         part = self.recipe == "shapenetpart"
+        want = self._recipe_draws()
         if self.draws == "numpy":
             d = self._host_draws(rs, idx)
-        elif not (self._fps_rows > 0 or self.train or part):
-            d = {}                        # a test split that takes the stored rows as they are: nothing is drawn
         else:
-            rows = None if s.lengths is None else s.lengths.index_select(0, item)
-            d = ops.cloud_draws(item, n, self.seed, self.epoch, rows=rows, rows_all=s.points.shape[1], start=self._fps_rows > 0,
-                                affine=self.train and not part, perm=self.train and not part, sel=part)
+            d = {}                        # (a test split that takes the stored rows as they are: nothing is drawn)
+            if any(want.values()):
+                rows = None if s.lengths is None else s.lengths.index_select(0, item)
+                d = ops.cloud_draws(item, n, self.seed, self.epoch, rows=rows, rows_all=s.points.shape[1], **want)
+            if self._aug_stages:
+                aug = ops.cloud_draws_aug(item, n, self.seed, self.epoch, **{st: True for st in self._aug_stages})
+                d.update({"aug_" + k: v for k, v in aug.items()})
         sel = d.get("sel")
+        if self.recipe == "shapenet55" and not self._fps_rows:
+            sel = d["perm"].to(torch.int64) if sel is None else sel      # random_sample: the rows in shuffled order, normalised in that order
+            d = {k: v for k, v in d.items() if k != "perm"}
         if self._fps_rows:
             xyz = s.points.index_select(0, item)
             if xyz.shape[1] != self._fps_rows or xyz.shape[2] != 3:
                 xyz = xyz[:, :self._fps_rows, :3].contiguous()
             sel, _ = ops.fps(xyz, n, d["start"])
-        out = ops.cloud_prep(s.points, item, n, sel=sel, lengths=s.lengths, normalize=self.recipe == "modelnet", scale=d.get("scale"),
+        out = ops.cloud_prep(s.points, item, n, sel=sel, lengths=s.lengths, normalize=self.recipe in FPS_RECIPES, scale=d.get("scale"),
                              shift=d.get("shift"), perm=d.get("perm"), seg_src=s.seg if part else None)
         target = s.labels.index_select(0, item)
+        if self._aug_stages:              # one more launch: the stages in order, the height column in its tail
+            aug = {k[4:]: v for k, v in d.items() if k.startswith("aug_")}
+            pc = ops.cloud_augment(out[0] if part else out, [kernel_stage(st, aug) for st in self._aug_stages], height=self.use_height)
+            return (pc, target.to(torch.int32).view(-1, 1), out[1]) if part else (pc, target)
         if part:
             return (add_height(out[0]) if self.use_height else out[0], target.to(torch.int32).view(-1, 1), out[1])
         return (add_height(out) if self.use_height else out, target)

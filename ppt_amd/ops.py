@@ -1872,3 +1872,92 @@ def philox4x32(counters, seed):
     _lib.check(_lib.lib().ppt_cloud_draws(None, 0, None, 0, 0, int(seed) & (2 ** 64 - 1), 0, None, None, None, None, None, _p(counters),
                                           counters.shape[0], _p(out), _stream()), "ppt_cloud_draws")
     return out
+
+
+# the reference's augmentations on a finished batch (csrc/cloud_augment.hip; ppt_amd/data/augment.py)
+AUG_STAGES = {"dropout": (1, ((torch.uint8, ("B", "n")),)), "scale": (2, ((torch.float64, ("B",)),)),
+              "shift": (3, ((torch.float64, ("B", 3)),)), "rotate": (4, ((torch.float64, ("B", 3, 3)),)),
+              "jitter": (5, ((torch.float64, ("B", "n", 3)),)),
+              "affine": (6, ((torch.float64, ("B", 3)), (torch.float64, ("B", 3)))), "height": (7, ())}
+AUG_MAX_STAGES = 8
+AUG_MAGNITUDES = ("max_dropout", "scale_low", "scale_high", "shift_range", "angle_sigma", "angle_clip", "jitter_sigma", "jitter_clip")
+AUG_DEFAULTS = dict(zip(AUG_MAGNITUDES, (0.875, 0.8, 1.25, 0.1, 0.06, 0.18, 0.01, 0.05)))      # data/dataset_3d.py:83-131
+
+
+def cloud_augment(pc, stages, *, height=False):
+    """pc [B, n, 3] f32 -> a new [B, n, 3] f32 tensor ([B, n, 4] with the height column when height=True or ("height",) closes the
+    list), the stages applied in order in one launch (ppt_cloud_augment_f32), each bit-identical to the reference's numpy:
+        ("dropout", mask [B, n] u8)   ("scale", s [B] f64)   ("shift", t [B, 3] f64)   ("rotate", R [B, 3, 3] f64)
+        ("jitter", noise [B, n, 3] f64)   ("affine", scale [B, 3] f64, shift [B, 3] f64)   ("height",)
+    At most 8 stages, the height column included; n <= 8192."""
+    stages = [tuple(s) for s in stages] + ([("height",)] if height else [])
+    for k, st in enumerate(stages):
+        if not st or st[0] not in AUG_STAGES:
+            raise ValueError(f"cloud_augment: unknown stage {st[0] if st else st!r}; one of {tuple(AUG_STAGES)}")
+        if len(st) - 1 != len(AUG_STAGES[st[0]][1]):
+            raise ValueError(f"cloud_augment: stage {st[0]!r} takes {len(AUG_STAGES[st[0]][1])} parameter arrays, got {len(st) - 1}")
+        if st[0] == "height" and k != len(stages) - 1:
+            raise ValueError("cloud_augment: the height column is taken from the finished cloud: 'height' must be the last stage")
+    if not 1 <= len(stages) <= AUG_MAX_STAGES:
+        raise ValueError(f"cloud_augment: between 1 and {AUG_MAX_STAGES} stages (the height column counts), got {len(stages)}")
+    _chk(pc, torch.float32, "pc")
+    if pc.dim() != 3 or pc.shape[2] != 3:
+        raise ValueError(f"pc must be [B, n, 3], got {tuple(pc.shape)}")
+    B, n, _ = pc.shape
+    arr = (_lib.AugStage * len(stages))()
+    for k, st in enumerate(stages):
+        kind, spec = AUG_STAGES[st[0]]
+        arr[k].kind = kind
+        for j, (t, (dtype, shape)) in enumerate(zip(st[1:], spec)):
+            _chk(t, dtype, f"{st[0]} parameter {j}")
+            want = tuple(B if d == "B" else n if d == "n" else d for d in shape)
+            if tuple(t.shape) != want:
+                raise ValueError(f"stage {st[0]!r}: parameter {j} must be {want}, got {tuple(t.shape)}")
+            setattr(arr[k], "ab"[j], t.data_ptr())
+    out = torch.empty((B, n, 4 if stages[-1][0] == "height" else 3), dtype=torch.float32, device=pc.device)
+    if profiler is not None:
+        profiler.begin("cloud_augment", float(B) * n * 28)
+    _lib.check(_lib.lib().ppt_cloud_augment_f32(_p(pc), B, n, arr, len(stages), _p(out), _stream()), "ppt_cloud_augment_f32")
+    if profiler is not None:
+        profiler.end()
+    return out
+
+
+def cloud_draws_aug(index, n, seed, epoch, *, dropout=False, scale=False, shift=False, rotate_perturbation=False, rotate=False,
+                    jitter=False, **magnitudes):
+    """The Philox4x32-10 draws of the augmentations for the samples `index` [B] i64 (ppt_cloud_draws_aug; slots 4-10, the layout is
+    stated in include/ppt_hip.h): a dict with the requested ones of
+        dropout              ratio [B] f64 in [0, max_dropout), mask [B, n] u8
+        scale                scale [B] f64 in [scale_low, scale_high)
+        shift                shift [B, 3] f64 in [-shift_range, shift_range)
+        rotate_perturbation  angles [B, 3] f64 = clip(angle_sigma N(0, 1), +-angle_clip), perturb [B, 3, 3] f64 = Rz (Ry Rx)
+        rotate               angle [B] f64 in [0, 2 pi), rotate [B, 3, 3] f64 about y
+        jitter               noise [B, n, 3] f64 = clip(jitter_sigma N(0, 1), +-jitter_clip)
+    magnitudes: any of AUG_MAGNITUDES; the defaults are the reference's (AUG_DEFAULTS)."""
+    unknown = set(magnitudes) - set(AUG_MAGNITUDES)
+    if unknown:
+        raise ValueError(f"cloud_draws_aug: unknown magnitude {sorted(unknown)}; one of {AUG_MAGNITUDES}")
+    if not (dropout or scale or shift or rotate_perturbation or rotate or jitter):
+        raise ValueError("cloud_draws_aug: nothing asked for")
+    _chk(index, torch.int64, "index")
+    B, dev = index.numel(), index.device
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)      # noqa: E731
+    out = {}
+    if dropout:
+        out["ratio"], out["mask"] = f64(B), torch.empty((B, n), dtype=torch.uint8, device=dev)
+    if scale:
+        out["scale"] = f64(B)
+    if shift:
+        out["shift"] = f64(B, 3)
+    if rotate_perturbation:
+        out["angles"], out["perturb"] = f64(B, 3), f64(B, 3, 3)
+    if rotate:
+        out["angle"], out["rotate"] = f64(B), f64(B, 3, 3)
+    if jitter:
+        out["noise"] = f64(B, n, 3)
+    mag = (ctypes.c_double * len(AUG_MAGNITUDES))(*[float(magnitudes.get(k, AUG_DEFAULTS[k])) for k in AUG_MAGNITUDES])
+    g = out.get
+    _lib.check(_lib.lib().ppt_cloud_draws_aug(_p(index), B, int(n), int(seed) & (2 ** 64 - 1), int(epoch) & 0xFFFFFFFF, mag, _p(g("ratio")),
+                                              _p(g("mask")), _p(g("scale")), _p(g("shift")), _p(g("angles")), _p(g("perturb")),
+                                              _p(g("angle")), _p(g("rotate")), _p(g("noise")), _stream()), "ppt_cloud_draws_aug")
+    return out

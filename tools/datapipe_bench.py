@@ -4,11 +4,16 @@ feeds.  The table of profiles/r08_datapipe.md comes from this tool.
 
     python tools/datapipe_bench.py                     # both stages, each as a child process under its own time limit
     python tools/datapipe_bench.py --stage loader      # (a) loader alone: clouds/s and host ms per batch, both draw modes, per recipe
+    python tools/datapipe_bench.py --stage loader --recipes modelnet,shapenet55 --draws device --window 0.5
+    python tools/datapipe_bench.py --stage loader --recipes modelnet --augment rotate,jitter --draws device --window 0.5
+                                                       # the augmentations (profiles/r22_augment.md): timed windows of >= 0.5 s
     python tools/datapipe_bench.py --stage steps       # (b) the step loop under resident / worker / device-loader feeding
     python tools/datapipe_bench.py --stage trace       # a short device-loader step loop, to run under rocprofv3 --kernel-trace --stats
 
 (a) B = 32, 8192 -> 1024 (ScanObjectNN: the first 1024 of 2048 rows; ShapeNetPart: choice of 2048 from ragged clouds of up to 2900
-rows).  Clock: host clock around whole epochs, ending in a device synchronise.  "host ms" is the time the launching thread spends
+rows; ShapeNet-55: ModelNet's clouds through recipe "shapenet55", i.e. FPS + ShapeNet's five augmentations).  --augment adds the named
+stages (DeviceBatchLoader(augment=...)) to every recipe measured.  --window S: a timed repeat runs whole epochs until S seconds have
+passed (default: one epoch per repeat).  Clock: host clock around whole epochs, ending in a device synchronise.  "host ms" is the time the launching thread spends
 inside next() per batch -- the draws (numpy mode), the launches, the event.
 (b) the three feeds ALTERNATE inside one process, after a warm-up of every feed; each timed block ends in a device synchronise:
     resident  the same resident batch every step, vouched ready (Trainer.inputs_ready): no feeding at all -- the yardstick
@@ -46,37 +51,49 @@ def stage_loader(a):
     pc, lab = synth_set(m, ROWS)
     r = np.random.default_rng(0)
     lens = r.integers(2100, 2900, size=m)
-    sets = {"modelnet": (DeviceCloudSet(pc, lab), NPOINTS),
-            "scanobjectnn": (DeviceCloudSet(pc[:, :2048].copy(), lab), NPOINTS),
-            "shapenetpart": (DeviceCloudSet([pc[i, :L] for i, L in enumerate(lens)], lab % 16,
-                                            seg=[r.integers(0, 50, L).astype(np.int32) for L in lens]), 2048)}
+    make = {"modelnet": lambda: (DeviceCloudSet(pc, lab), NPOINTS),
+            "scanobjectnn": lambda: (DeviceCloudSet(pc[:, :2048].copy(), lab), NPOINTS),
+            "shapenetpart": lambda: (DeviceCloudSet([pc[i, :L] for i, L in enumerate(lens)], lab % 16,
+                                                    seg=[r.integers(0, 50, L).astype(np.int32) for L in lens]), 2048),
+            "shapenet55": lambda: (DeviceCloudSet(pc, lab), NPOINTS)}
+    recipes = list(make) if a.recipes == "all" else a.recipes.split(",")
+    extra = {"augment": tuple(a.augment.split(","))} if a.augment else {}     # (no keyword at all without --augment)
     res = []
-    for recipe, (s, n) in sets.items():
-        for draws in ("device", "numpy"):
-            ld = DeviceBatchLoader(s, B, n, recipe, True, seed=1, draws=draws)
+    for recipe in recipes:
+        s, n = make[recipe]()
+        for draws in (("device", "numpy") if a.draws == "both" else (a.draws,)):
+            ld = DeviceBatchLoader(s, B, n, recipe, True, seed=1, draws=draws, **extra)
             for _ in ld:                                      # warm-up: code objects, allocator, pinned pool
                 pass
             rates, host_ms = [], []
+            batch_ms, epoch = [], 0
             for rep in range(a.repeats):
-                ld.set_epoch(rep + 1)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                it, spent, nb = iter(ld), 0.0, 0
-                while True:
-                    h0 = time.perf_counter()
-                    batch = next(it, None)
-                    spent += time.perf_counter() - h0
-                    if batch is None:
+                spent, nb = 0.0, 0
+                while True:                                   # whole epochs, each ending in a device synchronise
+                    epoch += 1
+                    ld.set_epoch(epoch)
+                    it = iter(ld)
+                    while True:
+                        h0 = time.perf_counter()
+                        batch = next(it, None)
+                        spent += time.perf_counter() - h0
+                        if batch is None:
+                            break
+                        nb += 1
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                    if dt >= a.window:
                         break
-                    nb += 1
-                torch.cuda.synchronize()
-                dt = time.perf_counter() - t0
                 rates.append(nb * B / dt)
                 host_ms.append(1e3 * spent / nb)
-            row = dict(recipe=recipe, draws=draws, npoints=n, clouds_per_s=[round(x) for x in rates],
+                batch_ms.append(1e3 * dt / nb)
+            row = dict(recipe=recipe, draws=draws, npoints=n, augment=list(extra.get("augment", ())), window_s=a.window,
+                       clouds_per_s=[round(x) for x in rates], ms_per_batch=[round(x, 4) for x in batch_ms],
                        host_ms_per_batch=[round(x, 3) for x in host_ms])
-            print(f"loader-alone {recipe:13s} draws={draws:6s} n={n}: clouds/s {row['clouds_per_s']}  host ms/batch {row['host_ms_per_batch']}",
-                  flush=True)
+            print(f"loader-alone {recipe:13s} draws={draws:6s} n={n} augment={a.augment or '-'}: clouds/s {row['clouds_per_s']}  "
+                  f"ms/batch {row['ms_per_batch']}  host ms/batch {row['host_ms_per_batch']}", flush=True)
             res.append(row)
     print("DATAPIPE_LOADER " + json.dumps(res), flush=True)
 
@@ -198,11 +215,16 @@ def main():
     ap.add_argument("--batches", type=int, default=32, help="batches of 32 clouds in the synthetic set (one epoch)")
     ap.add_argument("--epochs", type=int, default=4, help="epochs per timed block of the resident / device feeds")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--recipes", default="all", help="loader stage: comma-separated recipes (default: every recipe)")
+    ap.add_argument("--draws", default="both", choices=["both", "device", "numpy"], help="loader stage: the draw modes to time")
+    ap.add_argument("--augment", default="", help="loader stage: comma-separated augmentation stages added to each recipe, e.g. rotate,jitter")
+    ap.add_argument("--window", type=float, default=0.0, help="loader stage: seconds a timed repeat lasts at least (whole epochs)")
     a = ap.parse_args()
     if a.stage == "all":
         for st in ("loader", "steps"):                        # a fresh process per stage; a stage that fails ends the run
             cmd = [sys.executable, os.path.abspath(__file__), "--stage", st, "--batches", str(a.batches), "--epochs", str(a.epochs),
-                   "--repeats", str(a.repeats)]
+                   "--repeats", str(a.repeats), "--recipes", a.recipes, "--draws", a.draws, "--augment", a.augment,
+                   "--window", str(a.window)]
             r = subprocess.run(cmd, timeout=STAGE_LIMIT_S[st])
             if r.returncode != 0:
                 sys.exit(f"stage {st} exited with {r.returncode}")
