@@ -16,6 +16,16 @@
 //       round trip, no residual read in the epilogue.  DropPath's per-sample factor rides on the GELU output (rs * U) W2 = rs * (U W2);
 //   (4) the weights arrive through two register rings (fc1: 4 k-steps = 8 KiB, fc2: 4 k-steps = 12 KiB per wave; in the step, beside the other streams, the deeper fc2 ring is worth 2 %) that wrap from one
 //       slab into the next and from the last slab back to the first: the stream never stops at a phase boundary.
+//   (5) the prologue ISSUES every request of a chunk before it waits for one, in the order in which the waits come free (vmcnt
+//       retires in order) -- profiles/r23_vit_mlp3_prologue.md:
+//         constants (first chunk: 42 LDS-DMA pieces straight into gam | bet | b1s | b2s, no register in between)
+//         | with proj: the chunk's rows of `a` by LDS-DMA into the image, one 768-byte piece per row, rows round-robin over the waves
+//         | with proj: the first four k-steps of Wp | the residual rows | DropPath factors (both branches; pointer select, no branch)
+//       The image barrier waits for the `a` pieces with a COUNTED vmcnt (everything behind them stays in flight), the proj loop's
+//       counted waits cover Wp alone for its first four k-steps, x is first waited for where the ring refills behind it are
+//       needed / where x_mid = x + ... is formed, and the proj bias is requested under the loop's last four k-steps.  The kernel is
+//       a template on the proj form: one body, two register allocations (with the run-time branch hipcc spilled in both).
+//       Measured and removed: nothing; not built: the fc1 / fc2 rings under the proj MFMAs (the loop holds 251 of 256 VGPRs, the rings are 80).
 // Arithmetic differs from mlp_fused.hip only in rounding ORDER (residual first instead of last; rs folded before the 16-bit
 // rounding of U): tests/test_kernels_gpu.py holds both to the same bounds against fp32 math on the same operands.
 #include "ppt_common.h"
@@ -64,6 +74,13 @@ __device__ __forceinline__ float gelu_poly3(float x, float hs)
     return fmaf(h, e, h);
 }
 
+// lds_dma16's one-dword form (ppt_common.h): 64 lanes x 4 B -> 256 B of LDS starting at the wave-uniform `lds`, in lane order
+__device__ __forceinline__ void lds_dma4(const void *gsrc, void *lds)
+{
+    const uint32_t m0v = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)lds;
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" :: "v"(gsrc), "s"(m0v) : "memory", "m0");
+}
+
 #ifdef PPT_MLP3_STAMP
 #ifndef PPT_MLP3_STAMP_CHUNK
 #define PPT_MLP3_STAMP_CHUNK 0           /* which of the workgroup's chunks is stamped (1: the second -- warm instruction cache / TLBs) */
@@ -73,7 +90,7 @@ __device__ __forceinline__ float gelu_poly3(float x, float hs)
 #define MLP3_STAMP(j, slot) do { } while (0)
 #endif
 
-template <typename F>
+template <typename F, bool PROJ>
 __global__ __launch_bounds__(512, 2) void vit_mlp3_kernel(const ppt_vit_mlp_params p)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -124,58 +141,78 @@ __global__ __launch_bounds__(512, 2) void vit_mlp3_kernel(const ppt_vit_mlp_para
         lds_barrier();                                                   // the previous chunk's readers are done
         MLP3_STAMP(5, 1);
         // acc2[rb][nb]: columns 48 w + 16 nb + 4 kg .. + 3 of row 16 rb + l15.  It STARTS as the residual (x, or x_mid below).
-        // The residual rows are requested FIRST, in this layout, and nothing else reads x: the LayerNorm statistics are formed from
+        // The residual rows are requested in this layout, and nothing else reads x: the LayerNorm statistics are formed from
         // the accumulator layout too (first version: a separate 16-threads-per-row LayerNorm pass over x in three dependent
         // load -> reduce -> write rounds, then a second read of x for the accumulators -- 41 000 cycles of prologue per chunk).
         ppt_f32x4 acc2[RB][3];
-        float hrs[RB], rs1[RB];
+        float hrs[RB];
         uint4 g1[D1][2], g2[D2][3];                                      // the two weight rings
-        {
-            // (once per workgroup) the per-channel constants are REQUESTED first and stored to LDS behind the requests below: vmcnt
-            // retires in order, so stored behind requests issued EARLIER the ds_write waited for the residual rows to arrive from HBM
-            float cst[6];
-            const bool first = chunk == (int)blockIdx.x;
-            if (first) {
-                const int c = tid;
-                cst[0] = c < D ? p.ln_w[c] : 0.f; cst[1] = c < D ? p.ln_b[c] : 0.f; cst[2] = (c < D && p.b2) ? p.b2[c] : 0.f;
+        auto request_hrs = [&]() {
+            typedef const __attribute__((address_space(1))) float *gfloat_p;      // (behind the asm the pointer is generic: say again that it is global)
+            const float *rs = p.row_scale;
+            asm volatile("" : "+s"(rs));                                  // (opaque: the selects and the reciprocal stay in the chunk, not in registers across it)
+            const gfloat_p rsp = (gfloat_p)(rs ? rs : p.ln_w);
+            const int rsr = rs ? p.row_scale_rows : 0x7fffffff;
 #pragma unroll
-                for (int i = 0; i < 3; ++i) cst[3 + i] = p.b1 ? p.b1[c + 512 * i] : 0.f;
-            }
-            // ---- (a) the proj operand: the chunk's rows of the attention output -> LDS image (rows past the chunk: zeros), IN FRONT of
-            // every other request -- vmcnt retires in order, and behind the residual rows' requests these stores waited for HBM to
-            // deliver those first (9 200 cycles from the first request to the image's barrier).  (Held in registers across the
-            // other requests instead, eight uint4 per thread, hipcc spilled 84-136 registers.)
-            if (p.proj_a) {
-                const bf16_t *A = (const bf16_t *)p.proj_a;
-                for (int i = tid; i < R * (D / 8); i += 512) {
-                    const int lr = i / (D / 8), c8 = i % (D / 8);
-                    uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                    if (lr < nrow) v = *reinterpret_cast<const uint4 *>(A + (size_t)(row0 + lr) * D + 8 * c8);
-                    *reinterpret_cast<uint4 *>(h2 + lr * HP + 16 * c8) = v;
+            for (int rb = 0; rb < RB; ++rb) hrs[rb] = rsp[(row0 + min(16 * rb + l15, nrow - 1)) / rsr];
+        };
+        {
+            // Every request of the prologue is ISSUED before anything waits for one (vmcnt retires in order, so the order of the
+            // requests is the order in which their waits come free):
+            //   with proj:    constants (first chunk) | `a` rows (LDS-DMA) | first four k-steps of Wp | residual rows | DropPath factors
+            //   without:      constants (first chunk) | residual rows | DropPath factors
+            // and the waits are counted: the image barrier waits for the `a` pieces alone (and the constants' pieces in front of them),
+            // the proj loop's first four k-steps for Wp alone, and x is first waited for behind them.
+            const bool first = chunk == (int)blockIdx.x;
+            float4 xv[RB][3];
+            float fac1[RB];
+            // DropPath's per-sample factors are loaded UNCONDITIONALLY, through a wave-uniform pointer select (no factor: one readable
+            // word, ln_w[0], that the select below throws away).  Under pointer-null branches each of these loads was a basic block of
+            // its own and hipcc put s_waitcnt vmcnt(0) behind every one: the first drained the residual rows, the rest were serial trips.
+            auto request_x = [&]() {
+#pragma unroll
+                for (int rb = 0; rb < RB; ++rb) {
+                    const int m = row0 + min(16 * rb + l15, nrow - 1);
+#pragma unroll
+                    for (int nb = 0; nb < 3; ++nb) xv[rb][nb] = *reinterpret_cast<const float4 *>(p.x + (size_t)m * D + 48 * w + 16 * nb + 4 * kg);
+                }
+            };
+            // (once per workgroup) the per-channel constants go to their LDS arrays (gam | bet | b1s | b2s, contiguous) by LDS-DMA in 42
+            // pieces of 64 floats, round-robin over the waves, IN FRONT of every other request: whatever this wave waits for next
+            // covers them (vmcnt retires in order), and they pass through no register.  (Loaded into six registers per thread and stored
+            // from there, they were what hipcc spilled first whenever this prologue changed -- and every reload drained the queue.)
+            if (first) {
+#pragma unroll 1
+                for (int k = w; k < (3 * D + HID) / 64; k += 8) {
+                    const float *src = k < D / 64 ? p.ln_w + 64 * k : k < 2 * D / 64 ? p.ln_b + (64 * k - D)
+                                     : k < (2 * D + HID) / 64 ? (p.b1 ? p.b1 + (64 * k - 2 * D) : nullptr) : (p.b2 ? p.b2 + (64 * k - 2 * D - HID) : nullptr);
+                    if (src) lds_dma4(src + lane, gam + 64 * k);
+                    else gam[64 * k + lane] = 0.f;                        // (no bias: zeros)
                 }
             }
-            float4 xv[RB][3];
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) {
-                const int m = row0 + min(16 * rb + l15, nrow - 1);
-#pragma unroll
-                for (int nb = 0; nb < 3; ++nb) xv[rb][nb] = *reinterpret_cast<const float4 *>(p.x + (size_t)m * D + 48 * w + 16 * nb + 4 * kg);
-            }
-            // DropPath's per-sample factors (both branches), per row block of this lane: requested now, used far below
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) {
-                const int m = row0 + min(16 * rb + l15, nrow - 1);
-                hrs[rb] = p.row_scale ? 0.5f * p.row_scale[m / p.row_scale_rows] : 0.5f;     // HALF the MLP branch's DropPath factor
-                rs1[rb] = (p.proj_a && p.proj_row_scale) ? p.proj_row_scale[m / p.proj_row_scale_rows] : 1.0f;
-            }
-            if (first) {
-                const int c = tid;
-                if (c < D) { gam[c] = cst[0]; bet[c] = cst[1]; b2s[c] = cst[2]; }
-#pragma unroll
-                for (int i = 0; i < 3; ++i) b1s[c + 512 * i] = cst[3 + i];
-            }
-            MLP3_STAMP(5, 2);
-            if (p.proj_a) {
+            if constexpr (PROJ) {
+                // ---- (a) the proj operand: the chunk's rows of the attention output -> LDS image by LDS-DMA, one piece per image row (a
+                // row is 768 B = 48 lanes x 16 B, the pitch 800 B: a piece never spans rows), rows round-robin over the waves.  Rows past
+                // the chunk are not requested: the same wave stores zeros there.  (First version: global_load -> s_waitcnt vmcnt(0) ->
+                // ds_write per piece, 7-8 dependent round trips per thread with every CU doing the same, and every other request behind
+                // them.  Held in registers across the other requests instead, eight uint4 per thread, hipcc spilled 84-136 registers.)
+                // (A rolled loop over an OPAQUE copy of the wave id: unrolled, hipcc hoisted the ten rows' LDS addresses and row offsets out
+                // of the chunk loop into SGPRs it did not have -- 70 of them spilled into VGPR lanes, and the zeros to scratch.)
+                if (lane < 2 * D / 16) {
+                    int wv = w;
+                    asm volatile("" : "+s"(wv));
+                    const unsigned char *A = (const unsigned char *)p.proj_a + (size_t)(row0 + wv) * (2 * D) + lo16;
+                    unsigned char *img = h2 + wv * HP;
+#pragma unroll 1
+                    for (int lr = wv; lr < R; lr += 8, A += 8 * 2 * D, img += 8 * HP) {
+                        if (lr < nrow) lds_dma16(A, img);
+                        else {
+                            uint32_t z = 0;                               // (opaque: hoisted, the zero piece was four registers held across the slab loop)
+                            asm volatile("" : "+v"(z));
+                            *reinterpret_cast<uint4 *>(img + lo16) = make_uint4(z, z, z, z);
+                        }
+                    }
+                }
                 // ---- (b) acc2 = a . Wp^T, Wp in fragment order (ppt_vit_proj_retile: [w][12 nb + ks][lane][8]) four k-steps deep
                 const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.proj_W), 0, 8 * 36 * 64 * 16, 0x00020000);
                 auto pfrag = [&](int nb, int ks) {
@@ -186,6 +223,18 @@ __global__ __launch_bounds__(512, 2) void vit_mlp3_kernel(const ppt_vit_mlp_para
                 for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
                     for (int nb = 0; nb < 3; ++nb) wf[ks][nb] = pfrag(nb, ks);
+                __builtin_amdgcn_sched_barrier(0);                        // (the scheduler may not move requests across: the order IS the design)
+                request_x();
+                __builtin_amdgcn_sched_barrier(0);
+                const float *rsp1 = p.proj_row_scale ? p.proj_row_scale : p.ln_w;
+                const int rsr1 = p.proj_row_scale ? p.proj_row_scale_rows : 0x7fffffff;
+#pragma unroll
+                for (int rb = 0; rb < RB; ++rb) fac1[rb] = rsp1[(row0 + min(16 * rb + l15, nrow - 1)) / rsr1];
+                request_hrs();
+                MLP3_STAMP(5, 2);
+                // this wave's `a` pieces have landed: everything requested behind them (12 Wp fragments, 15 residual pieces, 10 factors)
+                // may still be in flight
+                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * 3 + RB * 3 + 2 * RB) : "memory");
                 lds_barrier();
                 MLP3_STAMP(5, 3);
 #pragma unroll
@@ -193,6 +242,7 @@ __global__ __launch_bounds__(512, 2) void vit_mlp3_kernel(const ppt_vit_mlp_para
 #pragma unroll
                     for (int nb = 0; nb < 3; ++nb) acc2[rb][nb] = ppt_f32x4{0.f, 0.f, 0.f, 0.f};
                 const unsigned char *ha = h2 + l15 * HP + 16 * kg;
+                float4 bp[3];
                 uint4 fp[2][RB];                                          // (the image fragments of k-step ks + 1 requested before the MFMAs of k-step ks: GEMM1 below)
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb) fp[0][rb] = *reinterpret_cast<const uint4 *>(ha + rb * 16 * HP);
@@ -210,22 +260,32 @@ __global__ __launch_bounds__(512, 2) void vit_mlp3_kernel(const ppt_vit_mlp_para
 #pragma unroll
                         for (int nb = 0; nb < 3; ++nb) wf[ks & 3][nb] = pfrag(nb, ks + 4);
                     }
+                    // the proj bias: requested under the last four k-steps, where the ring's slots fall free, through a pointer select
+                    // like the factors (in the combine each row block loaded it again and the fifteen loads were one exposed round trip)
+                    if (ks + 4 == K1) {
+                        const float *pb = p.proj_b ? p.proj_b : p.ln_w;
+#pragma unroll
+                        for (int nb = 0; nb < 3; ++nb) bp[nb] = *reinterpret_cast<const float4 *>(pb + 48 * w + 16 * nb + 4 * kg);
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 MLP3_STAMP(5, 4);
                 // ---- (c) x_mid = x + drop_path1 * (acc + bp): STAYS in acc2
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb) {
-                    const float r1 = rs1[rb];
+                    const float r1 = p.proj_row_scale ? fac1[rb] : 1.0f;
 #pragma unroll
                     for (int nb = 0; nb < 3; ++nb) {
-                        const int n = 48 * w + 16 * nb + 4 * kg;
-                        const float4 bv = p.proj_b ? *reinterpret_cast<const float4 *>(p.proj_b + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+                        const float4 bv = p.proj_b ? bp[nb] : make_float4(0.f, 0.f, 0.f, 0.f);
                         acc2[rb][nb][0] = (acc2[rb][nb][0] + bv.x) * r1 + xv[rb][nb].x; acc2[rb][nb][1] = (acc2[rb][nb][1] + bv.y) * r1 + xv[rb][nb].y;
                         acc2[rb][nb][2] = (acc2[rb][nb][2] + bv.z) * r1 + xv[rb][nb].z; acc2[rb][nb][3] = (acc2[rb][nb][3] + bv.w) * r1 + xv[rb][nb].w;
                     }
                 }
             } else {
+                request_x();
+                request_hrs();
+                if (first) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(RB * 3 + RB) : "memory");     // this wave's pieces of the constants have landed
+                MLP3_STAMP(5, 2);
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -234,6 +294,7 @@ __global__ __launch_bounds__(512, 2) void vit_mlp3_kernel(const ppt_vit_mlp_para
         }
         MLP3_STAMP(5, 5);
         RELANE();
+
         // the two rings, filled per chunk, BEHIND the residual / proj phase and in front of the statistics' five barriers (kept live
         // from kernel entry, wrapping from the last slab into the next chunk's first, hipcc spilled all 80 ring registers around
         // the prologue -- 81 scratch stores right behind the loads)
@@ -247,7 +308,7 @@ __global__ __launch_bounds__(512, 2) void vit_mlp3_kernel(const ppt_vit_mlp_para
         {
             float *psum = reinterpret_cast<float *>(ub);                  // [R][32] partials, then [R] mean / rstd behind them
             float *stat = psum + R * 32;
-            if (p.proj_a) lds_barrier();                                  // every wave is done reading `a` from the image
+            if constexpr (PROJ) lds_barrier();                                  // every wave is done reading `a` from the image
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
                 float sum = 0.f;
@@ -375,6 +436,8 @@ __global__ __launch_bounds__(512, 2) void vit_mlp3_kernel(const ppt_vit_mlp_para
 
         gemm1(0);
 #pragma unroll
+        for (int rb = 0; rb < RB; ++rb) hrs[rb] = p.row_scale ? 0.5f * hrs[rb] : 0.5f;           // HALF the MLP branch's DropPath factor
+#pragma unroll
         for (int q = 0; q < 2 * RB; ++q) gelu_pair(0, q);
         lds_barrier();
         MLP3_STAMP(6, 2);
@@ -478,7 +541,8 @@ extern "C" int ppt_vit_mlp3_bf16(const ppt_vit_mlp_params *pp, void *stream)
         if (!p.proj_W || (p.proj_row_scale && p.proj_row_scale_rows <= 0)) return PPT_EINVAL;
         if (((uintptr_t)p.proj_a | (uintptr_t)p.proj_W | (uintptr_t)p.proj_b) & 15) return PPT_EINVAL;
     }
-    PPT_RAISE_LDS_ONCE(LDS_BYTES, (const void *)vit_mlp3_kernel<bf16_t>, (const void *)vit_mlp3_kernel<f16_t>);
+    PPT_RAISE_LDS_ONCE(LDS_BYTES, (const void *)vit_mlp3_kernel<bf16_t, false>, (const void *)vit_mlp3_kernel<f16_t, false>,
+                       (const void *)vit_mlp3_kernel<bf16_t, true>, (const void *)vit_mlp3_kernel<f16_t, true>);
     const int cus = ppt_cu_count(ppt_stream(stream));
     // chunks of at most R rows, a whole number of rounds over the CUs, every chunk as full as the division allows (mlp_fused.hip)
     int wgs = p.workgroups > 0 ? p.workgroups : cus;
@@ -489,7 +553,10 @@ extern "C" int ppt_vit_mlp3_bf16(const ppt_vit_mlp_params *pp, void *stream)
     p.rows_per_chunk = (p.M + p.n_chunks - 1) / p.n_chunks;
     p.n_chunks = (p.M + p.rows_per_chunk - 1) / p.rows_per_chunk;
     const int grid = p.n_chunks < wgs ? p.n_chunks : wgs;
-    ppt_launch16(p.dtype, [&](auto f) { hipLaunchKernelGGL(vit_mlp3_kernel<decltype(f)>, dim3(grid), dim3(512), LDS_BYTES, ppt_stream(stream), p); });
+    ppt_launch16(p.dtype, [&](auto f) {
+        if (p.proj_a) hipLaunchKernelGGL((vit_mlp3_kernel<decltype(f), true>), dim3(grid), dim3(512), LDS_BYTES, ppt_stream(stream), p);
+        else hipLaunchKernelGGL((vit_mlp3_kernel<decltype(f), false>), dim3(grid), dim3(512), LDS_BYTES, ppt_stream(stream), p);
+    });
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }
