@@ -537,7 +537,7 @@ int ppt_mini_pointnet_conv12_bf16(const float *pts, int64_t M, const float *w1, 
  * y[m, :] = W . A[m, :] + gterm[m / 32, :], A [M,256] bf16 contiguous, W [512,256] bf16 (the local half of the weight), gterm
  * [M/32, 512] f32 (the global half applied to the group maxima, bias included), y [M,512] bf16; part_sum / part_m2 [M/32, 512]
  * (both or neither) receive the BatchNorm partials per 32-row chunk.  Same results as ppt_gemm with group_add + col_sum.
- * K = 256, N = 512, M % 32 == 0; anything else: PPT_EUNSUPPORTED. */
+ * K = 256, N = 512, M % 32 == 0; anything else: PPT_EUNSUPPORTED.  A, W, y and gterm 16-byte aligned (else PPT_EINVAL). */
 int ppt_mini_pointnet_conv3_bf16(const void *A, int64_t M, int K, const void *W, const float *gterm, int N, void *y, float *part_sum,
                                  float *part_m2, void *stream);
 
