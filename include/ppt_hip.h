@@ -54,7 +54,8 @@ const char *ppt_strerror(int code);
  *    ppt_partseg_predict / ppt_render_balls / ppt_render_balls_workspace_bytes (csrc/render.hip);
  *    ppt_attention_ragged_fwd (csrc/attention_ragged.hip); ppt_sentence_rows / ppt_template_ensemble / ppt_cosine_head
  *    (csrc/zeroshot.hip); ppt_ball_query_lt_f32 / ppt_pool_res_finish / ppt_cloud_height_f32 (csrc/pointnext.hip);
- *    ppt_cloud_augment_f32 / ppt_cloud_draws_aug (csrc/cloud_augment.hip).
+ *    ppt_cloud_augment_f32 / ppt_cloud_draws_aug (csrc/cloud_augment.hip);
+ *    ppt_train_meter_cls / ppt_train_meter_partseg (csrc/meters.hip); ppt_sgd_multi / ppt_adam_multi (csrc/optim.hip).
  * 6: ppt_gemm_params.split16 / split_a_pow2 / split_b_pow2 (new trailing fields: fp32 operands as hi + lo half pairs),
  *    ppt_attention_fwd_split16 / ppt_attention_bwd_split16 (new), ppt_pointmlp_cloud_rstd / ppt_pointmlp_pq (new).
  * 5: ppt_labels_check (new), ppt_gemm256 (new: the 256-row macro-tile GEMM core), ppt_set_gemm256 / ppt_get_gemm256 (new),
@@ -722,6 +723,15 @@ typedef struct ppt_adamw_tensor {
 } ppt_adamw_tensor;
 int ppt_adamw_multi(const ppt_adamw_tensor *tensors, int count, float lr, float beta1, float beta2, float eps, float weight_decay,
                     float grad_scale, uint64_t *skipped, void *stream);
+/* sgd_multi (ABI 7, additive): torch.optim.SGD(params, lr) with its defaults (main_cls.py:54-55: no momentum, no weight decay) for
+ *   `count` tensors in one launch per PPT_ADAMW_MAX_TENSORS: p -= lr * g.  The table is ppt_adamw_multi's; exp_avg, exp_avg_sq and
+ *   step are not read (NULL / 0 are fine).  grad_scale and skipped as for ppt_adamw_step. */
+int ppt_sgd_multi(const ppt_adamw_tensor *tensors, int count, float lr, float grad_scale, uint64_t *skipped, void *stream);
+/* adam_multi (ABI 7, additive): torch.optim.Adam without weight decay (main_cls.py:56-57) on ppt_adamw_multi's kernel and table:
+ *   the decay factor is exactly 1, the rest is the arithmetic above.  Hyper-parameters as doubles: 1 - beta1 and 1 - beta2 are
+ *   formed in double and rounded once, as torch forms them (a float beta2 = 0.999, Adam's default, leaves 1 - beta2 4.7e-5 off). */
+int ppt_adam_multi(const ppt_adamw_tensor *tensors, int count, double lr, double beta1, double beta2, double eps, float grad_scale,
+                   uint64_t *skipped, void *stream);
 int ppt_prompt_rows(const float *base, const int *slot, const float *tokens, const float *pos_rows, int rows, int W, float *out,
                     void *stream);
 int ppt_prompt_rows_bwd(const float *g, const int *rows_of, int max_rows, int n_tok, int W, float scale, float *d_tokens, void *stream);
@@ -884,6 +894,37 @@ int ppt_partseg_metrics_chunks(int N);
 int ppt_partseg_metrics(const float *logits, const int64_t *labels, float smoothing, int B, int N, int P,
                         const int32_t *part_start, const int32_t *part_count, int max_parts, int32_t *records, float *partial,
                         void *stream);
+
+/* ---- training meters (ABI 7, additive; csrc/meters.hip; host side: ppt_amd/recognition.py, ppt_amd/partseg.py) ----------------
+ * What train() of main_cls.py:200-217 / main_partseg.py:218-243 takes out of a step with .item() reads, as ONE launch per step on
+ * the caller's stream that folds the step into a running record of PPT_METER_REC doubles; the host reads the record once per
+ * epoch (and zeroes it for the next).  Nothing is allocated, nothing is read back, no floating-point atomics: the same sequence
+ * of calls writes the same bytes.
+ *   rec [PPT_METER_REC] f64 (8-byte aligned):
+ *     [0] sum of weight * loss   [1] sum of weight * acc   [2] sum of weight          (metered calls only)
+ *     [3] calls   [4] calls whose loss was not finite   [5] the last metered loss   [6] the last metered acc
+ *     [7] calls that saw a label outside its range ([0, C) / [0, P))
+ *   The sums are AverageMeter.update's (utils/utils.py:333-337): sum += val * n in double, call after call, val the fp32 figure
+ *   widened to double (what .item() returns), n = weight (1 in main_cls.py:216-217, the batch size in main_partseg.py:242-243).
+ *   metered == 0 (a step main_cls.py:209 skips with `continue`) updates [3], [4] and [7] only: the finite check sits in front.
+ *   loss: a device fp32 scalar.
+ * train_meter_cls: logits [B, C] f32, labels [B] i64.  acc = (float)correct / (float)B, the IEEE fp32 quotient; correct = rows whose
+ *   FIRST arg-max equals the label (torch.argmax's tie rule, main_cls.py:200-202).  A row with a NaN logit counts as wrong (where
+ *   torch.argmax names the first NaN: the loss of such a step is NaN and [4] stops the run), and so does a label outside [0, C).
+ * train_meter_partseg: logits [B, N, P] f32, labels [B, N] i64, part_start / part_count [P] int32 as for ppt_partseg_metrics.  The
+ *   masked arg-max of main_partseg.py:219-229: the cloud's category is the one labels[b, 0] belongs to, a point's prediction the
+ *   first arg-max over that category's part range plus the range start; correct counts prediction == label over all B * N points,
+ *   acc = (float)correct / (float)(B * N).  A cloud whose labels[b, 0] is outside [0, P) contributes no correct point and sets [7].
+ *   scratch [PPT_METER_SCRATCH] uint32, ALL ZERO before the first call: a cloud is split over several workgroups that add their
+ *   integer counts there with integer atomics; the last to arrive folds the step and leaves the scratch all zero again.
+ *   P <= 64, PPT_EUNSUPPORTED otherwise (nothing launched). */
+#define PPT_METER_REC 8
+#define PPT_METER_SCRATCH 4
+int ppt_train_meter_cls(const float *logits, const int64_t *labels, const float *loss, int B, int C, double weight, int metered,
+                        double *rec, void *stream);
+int ppt_train_meter_partseg(const float *logits, const int64_t *labels, const float *loss, int B, int N, int P,
+                            const int32_t *part_start, const int32_t *part_count, double weight, int metered, double *rec,
+                            uint32_t *scratch, void *stream);
 
 /* ---- few-shot linear probe (ABI 7, additive; csrc/logreg.hip; host side: ppt_amd/probe.py) ------------------------------------
  * What the reference's linear_probe.py:55,68,73 asks of sklearn.LogisticRegression(solver="lbfgs", penalty="l2", C=c).fit and

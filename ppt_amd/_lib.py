@@ -235,6 +235,9 @@ _SIGNATURES = {
     "ppt_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int,
                                c_float, c_void_p, c_void_p]),
     "ppt_adamw_multi": (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
+    "ppt_sgd_multi": (c_int, [c_void_p, c_int, c_float, c_float, c_void_p, c_void_p]),
+    "ppt_adam_multi": (c_int, [c_void_p, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_float, c_void_p,
+                               c_void_p]),
     "ppt_prompt_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "ppt_prompt_rows_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "ppt_convert": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p]),
@@ -256,6 +259,9 @@ _SIGNATURES = {
     "ppt_partseg_metrics_chunks": (c_int, [c_int]),
     "ppt_partseg_metrics": (c_int, [c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                     c_void_p]),
+    "ppt_train_meter_cls": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p]),
+    "ppt_train_meter_partseg": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_double, c_int,
+                                        c_void_p, c_void_p, c_void_p]),
     "ppt_logreg_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
     "ppt_logreg_fit_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_float),
                                    c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),

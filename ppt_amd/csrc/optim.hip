@@ -11,7 +11,8 @@
 //     order (owner-computes: deterministic, no atomics) -- the backward of the splice; scale = 1 / the text tower's gradient
 //     scale (ppt_amd/gradscale.py), a power of two;
 //   * adamw_multi: the same AdamW update for up to PPT_ADAMW_MAX_TENSORS tensors in ONE launch (the tensor table travels as a
-//     kernel argument) -- head_type >= 1 trains 4 ... 13 tensors, part segmentation 47.
+//     kernel argument) -- head_type >= 1 trains 4 ... 13 tensors, part segmentation 47;
+//   * sgd_multi: torch.optim.SGD(params, lr) (--optim sgd, main_cls.py:54-55) over the same table in ONE launch: p -= lr g.
 // Given a skip counter (the mixed 16-bit mode), both AdamW kernels leave an element whose gradient is not finite alone (parameter and
 // moments unchanged, gradient zeroed) and COUNT it in that device word, which the caller reads when it wants to (train.Trainer.nonfinite_grad_elements): the fp32 reference
 // cannot overflow where a 16-bit backward stage can, and main_cls.py:205-207 stops on a non-finite loss.
@@ -81,6 +82,37 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const adamw_table tb, 
     if (bad && skipped) atomicAdd(skipped, (unsigned long long)bad);
 }
 
+// the tensor table of ppt_sgd_multi: ppt_adamw_multi's without the moments (28 B per tensor)
+struct sgd_table {
+    float *p[PPT_ADAMW_MAX_TENSORS], *g[PPT_ADAMW_MAX_TENSORS];
+    int64_t n[PPT_ADAMW_MAX_TENSORS];
+    int first_block[PPT_ADAMW_MAX_TENSORS + 1];
+    int count;
+};
+
+// torch.optim.SGD(params, lr) with its defaults (main_cls.py:54-55: no momentum, no weight decay): p -= lr g
+__global__ __launch_bounds__(256) void sgd_multi_kernel(const sgd_table tb, float lr, float grad_scale,
+                                                        unsigned long long *__restrict__ skipped, int prio)
+{
+    PPT_PRIO(prio);
+    int t = 0;
+    while (t + 1 < tb.count && (int)blockIdx.x >= tb.first_block[t + 1]) ++t;
+    const int64_t base = (int64_t)((int)blockIdx.x - tb.first_block[t]) * 1024;
+    float *__restrict__ p = tb.p[t];
+    float *__restrict__ g = tb.g[t];
+    unsigned bad = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int64_t i = base + u * 256 + threadIdx.x;
+        if (i >= tb.n[t]) continue;
+        const float gi = g[i] * grad_scale;
+        if (skipped && !(fabsf(gi) <= 3.0e38f)) { g[i] = 0.f; ++bad; continue; }     // (the rule of adamw_element)
+        if (grad_scale != 1.f) g[i] = gi;
+        p[i] = p[i] - lr * gi;
+    }
+    if (bad && skipped) atomicAdd(skipped, (unsigned long long)bad);
+}
+
 __global__ __launch_bounds__(256) void prompt_rows_kernel(const float *__restrict__ base, const int *__restrict__ slot,
                                                           const float *__restrict__ tokens, const float *__restrict__ pos_rows,
                                                           int rows, int W, float *__restrict__ out, int prio)
@@ -144,8 +176,10 @@ extern "C" int ppt_adamw_step(float *p, float *g, float *exp_avg, float *exp_avg
     return PPT_OK;
 }
 
-extern "C" int ppt_adamw_multi(const ppt_adamw_tensor *tensors, int count, float lr, float beta1, float beta2, float eps,
-                               float weight_decay, float grad_scale, uint64_t *skipped, void *stream)
+// adamw_multi_kernel's launches for a table of any length.  beta1 / beta2 (double) feed the bias corrections; the per-element
+// coefficients arrive as the caller rounded them.
+static int adamw_multi_launch(const ppt_adamw_tensor *tensors, int count, double lr, double beta1, double beta2, float decay, float omb1,
+                              float b2, float omb2, float eps, float grad_scale, uint64_t *skipped, void *stream)
 {
     if (!tensors || count <= 0 || !(grad_scale > 0.f)) return PPT_EINVAL;
     for (int i = 0; i < count; ++i)
@@ -157,17 +191,57 @@ extern "C" int ppt_adamw_multi(const ppt_adamw_tensor *tensors, int count, float
         int64_t blocks = 0;
         for (int i = 0; i < tb.count; ++i) {
             const ppt_adamw_tensor &t = tensors[c0 + i];
-            const double bc1 = 1.0 - pow((double)beta1, t.step), bc2 = 1.0 - pow((double)beta2, t.step);
+            const double bc1 = 1.0 - pow(beta1, t.step), bc2 = 1.0 - pow(beta2, t.step);
             tb.p[i] = t.p; tb.g[i] = t.g; tb.m[i] = t.exp_avg; tb.v[i] = t.exp_avg_sq; tb.n[i] = t.n;
-            tb.step_size[i] = (float)((double)lr / bc1);
+            tb.step_size[i] = (float)(lr / bc1);
             tb.inv_sqrt_bc2[i] = (float)(1.0 / sqrt(bc2));
             tb.first_block[i] = (int)blocks;
             blocks += (t.n + 1023) / 1024;
             if (blocks > 0x7fffffff) return PPT_EUNSUPPORTED;
         }
         tb.first_block[tb.count] = (int)blocks;
-        hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, ppt_stream(stream), tb,
-                           (float)(1.0 - (double)lr * weight_decay), 1.0f - beta1, beta2, 1.0f - beta2, eps, grad_scale,
+        hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, ppt_stream(stream), tb, decay, omb1, b2, omb2, eps,
+                           grad_scale, (unsigned long long *)skipped, ppt_get_wave_priority());
+        PPT_CHECK_LAUNCH();
+    }
+    return PPT_OK;
+}
+
+extern "C" int ppt_adamw_multi(const ppt_adamw_tensor *tensors, int count, float lr, float beta1, float beta2, float eps,
+                               float weight_decay, float grad_scale, uint64_t *skipped, void *stream)
+{
+    return adamw_multi_launch(tensors, count, (double)lr, (double)beta1, (double)beta2, (float)(1.0 - (double)lr * weight_decay),
+                              1.0f - beta1, beta2, 1.0f - beta2, eps, grad_scale, skipped, stream);
+}
+
+// torch.optim.Adam(params, lr) as main_cls.py:56-57 builds it (no weight decay), on adamw_multi_kernel: the decay factor is exactly 1
+// and what is left is Adam's arithmetic.  The hyper-parameters travel as doubles: torch forms 1 - beta2 in double and rounds the
+// result, and with Adam's default beta2 = 0.999 a float beta2 leaves 1.0f - beta2 4.7e-5 off (AdamW's 0.98: 1e-6).
+extern "C" int ppt_adam_multi(const ppt_adamw_tensor *tensors, int count, double lr, double beta1, double beta2, double eps,
+                              float grad_scale, uint64_t *skipped, void *stream)
+{
+    return adamw_multi_launch(tensors, count, lr, beta1, beta2, 1.0f, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+                              grad_scale, skipped, stream);
+}
+
+extern "C" int ppt_sgd_multi(const ppt_adamw_tensor *tensors, int count, float lr, float grad_scale, uint64_t *skipped, void *stream)
+{
+    if (!tensors || count <= 0 || !(grad_scale > 0.f)) return PPT_EINVAL;
+    for (int i = 0; i < count; ++i)
+        if (!tensors[i].p || !tensors[i].g || tensors[i].n <= 0) return PPT_EINVAL;
+    for (int c0 = 0; c0 < count; c0 += PPT_ADAMW_MAX_TENSORS) {
+        sgd_table tb;
+        tb.count = count - c0 < PPT_ADAMW_MAX_TENSORS ? count - c0 : PPT_ADAMW_MAX_TENSORS;
+        int64_t blocks = 0;
+        for (int i = 0; i < tb.count; ++i) {
+            const ppt_adamw_tensor &t = tensors[c0 + i];
+            tb.p[i] = t.p; tb.g[i] = t.g; tb.n[i] = t.n;
+            tb.first_block[i] = (int)blocks;
+            blocks += (t.n + 1023) / 1024;
+            if (blocks > 0x7fffffff) return PPT_EUNSUPPORTED;
+        }
+        tb.first_block[tb.count] = (int)blocks;
+        hipLaunchKernelGGL(sgd_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, ppt_stream(stream), tb, lr, grad_scale,
                            (unsigned long long *)skipped, ppt_get_wave_priority());
         PPT_CHECK_LAUNCH();
     }

@@ -1331,6 +1331,39 @@ def partseg_metrics(logits, labels, smoothing, part_start, part_count, max_parts
                                               int(max_parts), _p(records), _p(partial), _stream()), "ppt_partseg_metrics")
 
 
+METER_REC, METER_SCRATCH = 8, 4                    # the training meters' record and scratch (include/ppt_hip.h)
+METER_KEYS = ("loss_sum", "acc_sum", "weight", "calls", "nonfinite", "last_loss", "last_acc", "bad_labels")
+
+
+def _meter_args(logits, labels, loss, rec):
+    _chk(logits, torch.float32, "logits"); _chk(labels, torch.int64, "labels"); _chk(loss, torch.float32, "loss")
+    _chk(rec, torch.float64, "rec")
+    assert loss.numel() == 1 and rec.numel() == METER_REC
+
+
+def train_meter_cls(logits, labels, loss, rec, weight=1.0, metered=True):
+    """One training step of main_cls.py:200-217 folded into the epoch's record rec [8] f64 (METER_KEYS; zeroed by the caller at
+    the start of the epoch): logits [B, C] f32, labels [B] i64, loss a device fp32 scalar.  One launch, no read (ppt_train_meter_cls)."""
+    _meter_args(logits, labels, loss, rec)
+    B, C = logits.shape
+    assert labels.shape == (B,)
+    _lib.check(_lib.lib().ppt_train_meter_cls(_p(logits), _p(labels), _p(loss), B, C, float(weight), int(bool(metered)), _p(rec),
+                                              _stream()), "ppt_train_meter_cls")
+
+
+def train_meter_partseg(logits, labels, loss, part_start, part_count, rec, scratch, weight=1.0, metered=True):
+    """One training step of main_partseg.py:218-243 folded into rec [8] f64: logits [B, N, P] f32, labels [B, N] i64, part_start /
+    part_count [P] i32 as for partseg_metrics; scratch [4] i32, all zero before the first call and after every call
+    (ppt_train_meter_partseg)."""
+    _meter_args(logits, labels, loss, rec)
+    _chk(part_start, torch.int32, "part_start"); _chk(part_count, torch.int32, "part_count"); _chk(scratch, torch.int32, "scratch")
+    B, N, P = logits.shape
+    assert labels.shape == (B, N) and part_start.numel() == P and part_count.numel() == P and scratch.numel() >= METER_SCRATCH
+    _lib.check(_lib.lib().ppt_train_meter_partseg(_p(logits), _p(labels), _p(loss), B, N, P, _p(part_start), _p(part_count),
+                                                  float(weight), int(bool(metered)), _p(rec), _p(scratch), _stream()),
+               "ppt_train_meter_partseg")
+
+
 def partseg_predict(logits, anchor, part_start, part_count, pred=None):
     """logits [B, N, P] f32, anchor [B] i64 (a part id that names the cloud's category: labels[:, 0]), part_start / part_count
     [P] i32 as for partseg_metrics -> pred [B, N] i32 (caller-owned, allocated when None): the first arg-max over the category's
@@ -1683,8 +1716,9 @@ def adamw_step(p, g, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, s
                                          int(step), float(grad_scale), _p(skipped), _stream()), "ppt_adamw_step")
 
 
-def adamw_multi(items, lr, beta1, beta2, eps, weight_decay, grad_scale=1.0, skipped=None):
-    """The same update for a list of (p, g, exp_avg, exp_avg_sq, step) in one launch per 64 tensors (ppt_adamw_multi)."""
+def adamw_multi(items, lr, beta1, beta2, eps, weight_decay, grad_scale=1.0, skipped=None, adam=False):
+    """The same update for a list of (p, g, exp_avg, exp_avg_sq, step) in one launch per 64 tensors (ppt_adamw_multi).
+    adam=True: torch.optim.Adam without weight decay on the same kernel (ppt_adam_multi: the hyper-parameters as doubles)."""
     arr = (_lib.AdamwTensor * len(items))()
     for a, (p, g, m, v, step) in zip(arr, items):
         for t, nm in ((p, "p"), (g, "g"), (m, "exp_avg"), (v, "exp_avg_sq")):
@@ -1693,8 +1727,27 @@ def adamw_multi(items, lr, beta1, beta2, eps, weight_decay, grad_scale=1.0, skip
         a.p, a.g, a.exp_avg, a.exp_avg_sq, a.n, a.step = _p(p), _p(g), _p(m), _p(v), p.numel(), int(step)
     if skipped is not None:
         _chk(skipped, torch.int64, "skipped")
+    if adam:
+        assert weight_decay == 0, "Adam's weight_decay is an L2 term on the gradient, not AdamW's decay: not covered"
+        _lib.check(_lib.lib().ppt_adam_multi(ctypes.cast(arr, ctypes.c_void_p), len(items), lr, beta1, beta2, eps, float(grad_scale),
+                                             _p(skipped), _stream()), "ppt_adam_multi")
+        return
     _lib.check(_lib.lib().ppt_adamw_multi(ctypes.cast(arr, ctypes.c_void_p), len(items), lr, beta1, beta2, eps, weight_decay,
                                           float(grad_scale), _p(skipped), _stream()), "ppt_adamw_multi")
+
+
+def sgd_multi(items, lr, grad_scale=1.0, skipped=None):
+    """torch.optim.SGD(params, lr)'s update p -= lr * g for a list of (p, g) in one launch per 64 tensors (ppt_sgd_multi); the
+    non-finite skip and count of adamw_step."""
+    arr = (_lib.AdamwTensor * len(items))()
+    for a, (p, g) in zip(arr, items):
+        _chk(p, torch.float32, "p"); _chk(g, torch.float32, "g")
+        assert g.numel() == p.numel()
+        a.p, a.g, a.n = _p(p), _p(g), p.numel()
+    if skipped is not None:
+        _chk(skipped, torch.int64, "skipped")
+    _lib.check(_lib.lib().ppt_sgd_multi(ctypes.cast(arr, ctypes.c_void_p), len(items), lr, float(grad_scale), _p(skipped), _stream()),
+               "ppt_sgd_multi")
 
 
 def prompt_rows(base, slot, tokens, pos_rows):

@@ -201,18 +201,31 @@ class _CrossEntropyRows(torch.autograd.Function):
         return dlogits * (dloss * scale), None, None, None
 
 
+_OPTIM_KINDS = {torch.optim.AdamW: "adamw", torch.optim.Adam: "adam", torch.optim.SGD: "sgd"}      # main_cls.py:54-60, by exact type
+
+
 class Trainer:
     """One object per rank.  `step(pc, label)` == one iteration of main_cls.py:179-214."""
 
     def __init__(self, model, lr=3e-3, betas=(0.9, 0.98), eps=1e-8, wd=0.1, label_smoothing=0.2,
-                 lr_schedule=None, distributed=None, capturable=False):
+                 lr_schedule=None, distributed=None, capturable=False, optim="adamw"):
         self.model = model
         self.criterion = nn.CrossEntropyLoss(label_smoothing=label_smoothing)       # main_cls.py:52
         # main_cls.py:55-60 builds AdamW over ALL parameters; frozen ones never get a grad and are skipped by step().
         # Here the frozen ones are left out (380 tensors the optimizer would walk every step); reference_optimizer_state
         # re-indexes the state dict to the reference's layout for checkpoints.
-        self.optimizer = torch.optim.AdamW([p for p in model.parameters() if p.requires_grad], lr=lr, betas=betas,
-                                           eps=eps, weight_decay=wd, capturable=capturable)
+        trained = [p for p in model.parameters() if p.requires_grad]
+        if optim == "adamw":
+            self.optimizer = torch.optim.AdamW(trained, lr=lr, betas=betas, eps=eps, weight_decay=wd, capturable=capturable)
+        elif optim == "adam":
+            # --optim adam, main_cls.py:56-57: torch's defaults but for lr (betas, eps and wd are NOT passed on).  It steps on the
+            # AdamW kernel with a decay factor of exactly 1: what is left is Adam's arithmetic (ppt_adam_multi: the same kernel,
+            # hyper-parameters as doubles -- Adam's beta2 = 0.999 as a float would leave 1 - beta2 4.7e-5 off).
+            self.optimizer = torch.optim.Adam(trained, lr=lr)
+        elif optim == "sgd":
+            self.optimizer = torch.optim.SGD(trained, lr=lr)                        # --optim sgd, main_cls.py:54-55; ppt_sgd_multi
+        else:
+            raise ValueError(f"Trainer: optim must be 'adamw', 'adam' or 'sgd', got {optim!r}")
         # One launch per trained tensor (ppt_adamw_step: torch.optim.AdamW's arithmetic; csrc/optim.hip) instead of the ~10
         # multi-tensor kernels of the foreach implementation, while few tensors train: every kernel of the prompt chain costs a
         # dispatch round trip.  The torch optimizer object stays the owner of hyper-parameters and state (state_dict()).
@@ -569,11 +582,20 @@ class Trainer:
     def _optimizer_step(self, inv_scale=1.0):
         """AdamW over the tensors that got a gradient: ONE launch (ppt_adamw_step for a single tensor, ppt_adamw_multi for up to
         64 per launch: torch.optim.AdamW's arithmetic, state kept in the torch optimizer) instead of the ~10 multi-tensor kernels
-        of the foreach implementation.  inv_scale: for callers that scaled their loss themselves (folded in first)."""
+        of the foreach implementation.  inv_scale: for callers that scaled their loss themselves (folded in first).
+        Trainer(optim="adam" | "sgd"): the same launch shape on ppt_adam_multi / ppt_sgd_multi."""
         opt = self.optimizer
         params = [(g, p) for g in opt.param_groups for p in g['params'] if p.grad is not None]
-        if not (self.fused_adamw and params and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
-                                                    and p.grad.is_contiguous() and p.grad.dtype == torch.float32 for _, p in params)
+        # the fused path is keyed on the optimizer's TYPE (torch.optim.AdamW subclasses Adam: no isinstance): AdamW as ever; Adam on
+        # the same kernels where its weight_decay (an L2 term added to the gradient, not AdamW's decay) is 0, which is how
+        # main_cls.py:57 builds it; SGD as main_cls.py:55 builds it (no momentum, no weight decay) on ppt_sgd_multi
+        kind = _OPTIM_KINDS.get(type(opt))
+        plain = kind == "adamw" or \
+            (kind == "adam" and not any(g.get('weight_decay') or g.get('decoupled_weight_decay') for g, _ in params)) or \
+            (kind == "sgd" and not any(g.get('momentum') or g.get('weight_decay') or g.get('nesterov') for g, _ in params))
+        if not (self.fused_adamw and params and plain
+                and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
+                        and p.grad.is_contiguous() and p.grad.dtype == torch.float32 for _, p in params)
                 and not any(g.get('amsgrad') or g.get('maximize') for g, _ in params)):
             if inv_scale != 1.0 and params:
                 with torch.no_grad():
@@ -593,7 +615,15 @@ class Trainer:
         prio = self.model.chain_priority() if hasattr(self.model, "chain_priority") else 0
         with torch.no_grad(), ops.wave_priority(prio):
             by_group = {}
-            for g, p in params:
+            if kind == "sgd":                                # no state: torch.optim.SGD keeps none without momentum
+                for g, p in params:
+                    by_group.setdefault(id(g), (g, []))[1].append((p.data, p.grad))
+                for g, items in by_group.values():
+                    ops.sgd_multi(items, float(g['lr']), grad_scale=inv_scale, skipped=self._skipped if guard else None)
+                params_state, by_group = (), {}
+            else:
+                params_state = params
+            for g, p in params_state:
                 st = opt.state[p]
                 if not st:                                   # the layout torch.optim.AdamW._init_group creates
                     st['step'] = torch.tensor(0.0, dtype=torch.float32)
@@ -604,7 +634,9 @@ class Trainer:
             for g, items in by_group.values():
                 b1, b2 = g['betas']
                 hyper = (float(g['lr']), float(b1), float(b2), float(g['eps']), float(g['weight_decay']))
-                if len(items) == 1:
+                if kind == "adam":
+                    ops.adamw_multi(items, *hyper, grad_scale=inv_scale, skipped=self._skipped if guard else None, adam=True)
+                elif len(items) == 1:
                     p_, g_, m_, v_, step = items[0]
                     ops.adamw_step(p_, g_, m_, v_, *hyper, step, grad_scale=inv_scale, skipped=self._skipped if guard else None)
                 else:
