@@ -55,7 +55,9 @@ const char *ppt_strerror(int code);
  *    ppt_attention_ragged_fwd (csrc/attention_ragged.hip); ppt_sentence_rows / ppt_template_ensemble / ppt_cosine_head
  *    (csrc/zeroshot.hip); ppt_ball_query_lt_f32 / ppt_pool_res_finish / ppt_cloud_height_f32 (csrc/pointnext.hip);
  *    ppt_cloud_augment_f32 / ppt_cloud_draws_aug (csrc/cloud_augment.hip);
- *    ppt_train_meter_cls / ppt_train_meter_partseg (csrc/meters.hip); ppt_sgd_multi / ppt_adam_multi (csrc/optim.hip).
+ *    ppt_train_meter_cls / ppt_train_meter_partseg (csrc/meters.hip); ppt_sgd_multi / ppt_adam_multi (csrc/optim.hip);
+ *    ppt_fps_ragged_f32 / ppt_knn_group_ragged_f32 / ppt_ball_query_ragged_f32 / ppt_ball_query_multi_ragged_f32 (csrc/fps.hip,
+ *    csrc/knn_group.hip: per-cloud row counts).
  * 6: ppt_gemm_params.split16 / split_a_pow2 / split_b_pow2 (new trailing fields: fp32 operands as hi + lo half pairs),
  *    ppt_attention_fwd_split16 / ppt_attention_bwd_split16 (new), ppt_pointmlp_cloud_rstd / ppt_pointmlp_pq (new).
  * 5: ppt_labels_check (new), ppt_gemm256 (new: the 256-row macro-tile GEMM core), ppt_set_gemm256 / ppt_get_gemm256 (new),
@@ -115,6 +117,30 @@ typedef struct ppt_ball_multi {
     float *gxyz[3];
 } ppt_ball_multi;
 int ppt_ball_query_multi_f32(const float *xyz, const float *center, int B, int N, int S, const ppt_ball_multi *q, void *stream);
+
+/* ---- ragged clouds: H1 / H2 / H7 with a row count per cloud ----------------------------------------
+ * The same kernel bodies as the four entry points above, instantiated with a compile-time flag (those run the instantiation
+ * without it, n = N: the code they ran before these existed).  xyz is still
+ * [B,Nmax,3]: Nmax is the row stride and takes the size limits stated for N above; lengths [B] i32 on the device.  Cloud b
+ * is rows 0 .. lengths[b]-1 of its slab and nothing behind them is read, so the padding may hold anything (NaN included).
+ * The result for cloud b is bit-identical to the uniform entry point run on that cloud alone at N = lengths[b]:
+ *   fps         rows >= n are padding (distance 0, never a winner); with n < M the picks repeat as a lone cloud's do
+ *               (index 0 once every distance is 0); start[b] is clamped to [0, n-1]; the template follows Nmax (the arg-max
+ *               is an integer reduction: the picks do not depend on it)
+ *   knn_group   precondition k <= lengths[b] for every b, which the entry point cannot check (it does check k <= Nmax).  A
+ *               cloud that violates it gets slots 0 .. n-1 in order and slot 0's neighbour in slots n .. k-1: that is memory
+ *               safety, NOT a reference semantic (the reference's topk raises)
+ *   ball_query  the "nothing inside the ball" fill value is the cloud's own n; grouped_xyz clamps it to n-1
+ * A length outside 1 .. Nmax is the caller's error; the kernels clamp it into that range so that no access leaves the slab.
+ * PPT_EINVAL for lengths == NULL and for everything the uniform entry point refuses. */
+int ppt_fps_ragged_f32(const float *xyz, int B, int Nmax, int M, const int64_t *start, const int32_t *lengths,
+                       int64_t *out_idx, float *out_xyz, void *stream);
+int ppt_knn_group_ragged_f32(const float *xyz, const float *center, int B, int Nmax, int G, int k, const int32_t *lengths,
+                             int64_t *nbr_idx, float *neighborhood, float *nbr_dist, void *stream);
+int ppt_ball_query_ragged_f32(const float *xyz, const float *center, int B, int Nmax, int S, float radius_sq, int K,
+                              const int32_t *lengths, int64_t *idx, float *grouped_xyz, void *stream);
+int ppt_ball_query_multi_ragged_f32(const float *xyz, const float *center, int B, int Nmax, int S, const int32_t *lengths,
+                                    const ppt_ball_multi *q, void *stream);
 
 /* ---- GEMM with fused prologue / epilogue ----------------------------------------------------
  * C[M,N] = epilogue( prologue(A)[M,K] . B[N,K]^T ).  A and B are K-contiguous (torch Linear /

@@ -27,14 +27,19 @@ struct __align__(16) fps_slot {
     uint32_t pad[3];
 };
 
+// RAGGED (ppt_fps_ragged_f32): lengths [B] gives every cloud's own row count -- cloud b is rows 0 .. n-1 of its N-row slab,
+// n = lengths[b]; rows >= n are padding exactly as rows >= N of the last tile are (distance 0, never a winner) and are never read.
+// A template flag, and `lengths` the last argument: the uniform instantiation is the kernel it was before the flag existed (a
+// run-time `lengths == NULL` test cost the 1024-point launch 1.2 us of 223.5, profiles/r26_ragged_clouds.md).
 // XYZ_LDS: the cloud is also kept in LDS (12 N bytes, N <= 8192) and the loop tracks only (distance, index) per point;
 // the winner's coordinates are one broadcast LDS read per step instead of three selects per point plus three
 // v_readlane per wave (the per-point work is what bounds the big clouds: 8192 points, 16 waves: 1.94 -> ~1.3 us per pick).
-template <int PPT, int W, bool XYZ_LDS>
+template <int PPT, int W, bool XYZ_LDS, bool RAGGED>
 __global__ __launch_bounds__(W * 64) void fps_kernel(const float *__restrict__ xyz, int N, int M,
                                                      const int64_t *__restrict__ start,
                                                      int64_t *__restrict__ out_idx,
-                                                     float *__restrict__ out_xyz)
+                                                     float *__restrict__ out_xyz,
+                                                     const int32_t *__restrict__ lengths)
 {
     constexpr int T = W * 64;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -46,25 +51,27 @@ __global__ __launch_bounds__(W * 64) void fps_kernel(const float *__restrict__ x
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int b = blockIdx.x;
     const float *p = xyz + (size_t)b * N * 3;
+    const int n = RAGGED ? max(1, min((int)lengths[b], N)) : N;          // (clamped: a bad length must not leave the slab)
 
     float px[PPT], py[PPT], pz[PPT], dist[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
         const int i = t + j * T;
-        if (i < N) {
+        if (i < n) {
             px[j] = p[i * 3 + 0]; py[j] = p[i * 3 + 1]; pz[j] = p[i * 3 + 2];
             dist[j] = 1e10f;                      // misc.py:57
         } else {
             px[j] = py[j] = pz[j] = 0.0f;
-            dist[j] = 0.0f;                       // padding: never beats a real point (index >= N loses ties)
+            dist[j] = 0.0f;                       // padding: never beats a real point (index >= n loses ties)
         }
     }
 
     if constexpr (XYZ_LDS) {
-        for (int i = t; i < N * 3; i += T) cloud[i] = p[i];
+        for (int i = t; i < n * 3; i += T) cloud[i] = p[i];
         __syncthreads();
     }
     int cur = (int)start[b];
+    if constexpr (RAGGED) cur = max(0, min(cur, n - 1));                 // (a start behind the cloud's end must not leave it either)
     float cx = p[cur * 3 + 0], cy = p[cur * 3 + 1], cz = p[cur * 3 + 2];
 
     for (int it = 0; it < M; ++it) {
@@ -151,29 +158,52 @@ __global__ __launch_bounds__(W * 64) void fps_kernel(const float *__restrict__ x
         for (int i = t; i < M * 3; i += T) out_xyz[(size_t)b * M * 3 + i] = xyz_list[i];
 }
 
-template <int PPT, int W, bool XYZ_LDS>
-int launch_fps_v(const float *xyz, int B, int N, int M, const int64_t *start, int64_t *out_idx,
+template <int PPT, int W, bool XYZ_LDS, bool RAGGED>
+int launch_fps_v(const float *xyz, int B, int N, int M, const int64_t *start, const int32_t *lengths, int64_t *out_idx,
                  float *out_xyz, hipStream_t s, size_t lds)
 {
     // opt-in to > 64 KB of dynamic LDS: once per kernel instance (thread-safe static initialisation), to the device limit
-    static const hipError_t optin = hipFuncSetAttribute((const void *)fps_kernel<PPT, W, XYZ_LDS>,
+    static const hipError_t optin = hipFuncSetAttribute((const void *)fps_kernel<PPT, W, XYZ_LDS, RAGGED>,
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (lds > 64 * 1024 && optin != hipSuccess) return PPT_ELAUNCH;
-    hipLaunchKernelGGL((fps_kernel<PPT, W, XYZ_LDS>), dim3(B), dim3(W * 64), lds, s, xyz, N, M, start, out_idx, out_xyz);
+    hipLaunchKernelGGL((fps_kernel<PPT, W, XYZ_LDS, RAGGED>), dim3(B), dim3(W * 64), lds, s, xyz, N, M, start, out_idx, out_xyz, lengths);
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }
 
 template <int PPT, int W>
-int launch_fps(const float *xyz, int B, int N, int M, const int64_t *start, int64_t *out_idx,
+int launch_fps(const float *xyz, int B, int N, int M, const int64_t *start, const int32_t *lengths, int64_t *out_idx,
                float *out_xyz, hipStream_t s)
 {
     const size_t base = sizeof(fps_slot) * 2 * W + (size_t)M * 4 + (size_t)M * 12;
     const size_t with_cloud = base + (size_t)N * 12;
     static const int allow = [] { const char *e = getenv("PPT_FPS_XYZ_LDS"); return e ? atoi(e) : 1; }();
-    if (allow && with_cloud <= 150 * 1024) return launch_fps_v<PPT, W, true>(xyz, B, N, M, start, out_idx, out_xyz, s, with_cloud);
+    if (allow && with_cloud <= 150 * 1024) {
+        return lengths ? launch_fps_v<PPT, W, true, true>(xyz, B, N, M, start, lengths, out_idx, out_xyz, s, with_cloud)
+                       : launch_fps_v<PPT, W, true, false>(xyz, B, N, M, start, lengths, out_idx, out_xyz, s, with_cloud);
+    }
     if (base > 160 * 1024) return PPT_EUNSUPPORTED;
-    return launch_fps_v<PPT, W, false>(xyz, B, N, M, start, out_idx, out_xyz, s, base);
+    return lengths ? launch_fps_v<PPT, W, false, true>(xyz, B, N, M, start, lengths, out_idx, out_xyz, s, base)
+                   : launch_fps_v<PPT, W, false, false>(xyz, B, N, M, start, lengths, out_idx, out_xyz, s, base);
+}
+
+// the template follows N (the slab's row count) for ragged launches too: the arg-max is an integer reduction, so the picks do
+// not depend on how the points are dealt to lanes
+int fps_dispatch(const float *xyz, int B, int N, int M, const int64_t *start, const int32_t *lengths, int64_t *out_idx,
+                 float *out_xyz, void *stream)
+{
+    if (!xyz || !start || !out_idx || B <= 0 || N <= 0 || M <= 0 || N > 16384) return PPT_EINVAL;
+    hipStream_t s = ppt_stream(stream);
+    if (N <= 256) return launch_fps<1, 4>(xyz, B, N, M, start, lengths, out_idx, out_xyz, s);
+    if (N <= 512) return launch_fps<2, 4>(xyz, B, N, M, start, lengths, out_idx, out_xyz, s);
+    // points per lane x waves, measured with the cloud in LDS (tools/fps_bench.py, B = 32): more waves only lengthen the
+    // barrier and the slot fold -- 8192 points: <8,16> 732 us, <16,8> 495 us, <32,4> 558 us; 2048: <4,8> 300, <8,4> 286,
+    // <16,2> 326; 1024: <4,4> 234, <8,2> 244, <16,1> 302
+    if (N <= 1024) return launch_fps<4, 4>(xyz, B, N, M, start, lengths, out_idx, out_xyz, s);
+    if (N <= 2048) return launch_fps<8, 4>(xyz, B, N, M, start, lengths, out_idx, out_xyz, s);
+    if (N <= 4096) return launch_fps<16, 4>(xyz, B, N, M, start, lengths, out_idx, out_xyz, s);
+    if (N <= 8192) return launch_fps<16, 8>(xyz, B, N, M, start, lengths, out_idx, out_xyz, s);
+    return launch_fps<16, 16>(xyz, B, N, M, start, lengths, out_idx, out_xyz, s);
 }
 
 }  // namespace
@@ -181,16 +211,12 @@ int launch_fps(const float *xyz, int B, int N, int M, const int64_t *start, int6
 extern "C" int ppt_fps_f32(const float *xyz, int B, int N, int M, const int64_t *start, int64_t *out_idx,
                            float *out_xyz, void *stream)
 {
-    if (!xyz || !start || !out_idx || B <= 0 || N <= 0 || M <= 0 || N > 16384) return PPT_EINVAL;
-    hipStream_t s = ppt_stream(stream);
-    if (N <= 256) return launch_fps<1, 4>(xyz, B, N, M, start, out_idx, out_xyz, s);
-    if (N <= 512) return launch_fps<2, 4>(xyz, B, N, M, start, out_idx, out_xyz, s);
-    // points per lane x waves, measured with the cloud in LDS (tools/fps_bench.py, B = 32): more waves only lengthen the
-    // barrier and the slot fold -- 8192 points: <8,16> 732 us, <16,8> 495 us, <32,4> 558 us; 2048: <4,8> 300, <8,4> 286,
-    // <16,2> 326; 1024: <4,4> 234, <8,2> 244, <16,1> 302
-    if (N <= 1024) return launch_fps<4, 4>(xyz, B, N, M, start, out_idx, out_xyz, s);
-    if (N <= 2048) return launch_fps<8, 4>(xyz, B, N, M, start, out_idx, out_xyz, s);
-    if (N <= 4096) return launch_fps<16, 4>(xyz, B, N, M, start, out_idx, out_xyz, s);
-    if (N <= 8192) return launch_fps<16, 8>(xyz, B, N, M, start, out_idx, out_xyz, s);
-    return launch_fps<16, 16>(xyz, B, N, M, start, out_idx, out_xyz, s);
+    return fps_dispatch(xyz, B, N, M, start, nullptr, out_idx, out_xyz, stream);
+}
+
+extern "C" int ppt_fps_ragged_f32(const float *xyz, int B, int Nmax, int M, const int64_t *start, const int32_t *lengths,
+                                  int64_t *out_idx, float *out_xyz, void *stream)
+{
+    if (!lengths) return PPT_EINVAL;
+    return fps_dispatch(xyz, B, Nmax, M, start, lengths, out_idx, out_xyz, stream);
 }

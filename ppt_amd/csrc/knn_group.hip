@@ -44,6 +44,17 @@ __device__ __forceinline__ uint32_t wave_kth_smallest(uint32_t v, int k)
     return T;
 }
 
+// RAGGED launches (ppt_*_ragged_f32): lengths [B] gives every cloud's own row count n <= N inside its N-row slab; everything
+// below walks n, rows >= n are never read.  Not RAGGED: n = N, lengths is not looked at.  A template flag, and `lengths` the last
+// argument, so that the uniform instantiations are the kernels they were before the flag existed (profiles/r26_ragged_clouds.md).
+// (Clamped: a bad length must not leave the slab.)
+template <bool RAGGED>
+__device__ __forceinline__ int cloud_rows(const int32_t *__restrict__ lengths, int b, int N)
+{
+    if constexpr (RAGGED) return max(1, min((int)lengths[b], N));
+    return N;
+}
+
 __device__ __forceinline__ void stage_cloud(const float *__restrict__ p, int N, float4 *cloud)
 {
     for (int i = threadIdx.x; i < N; i += blockDim.x) {
@@ -52,11 +63,12 @@ __device__ __forceinline__ void stage_cloud(const float *__restrict__ p, int N, 
     }
 }
 
-template <int W>
+template <int W, bool RAGGED>
 __global__ __launch_bounds__(W * 64) void knn_group_kernel(const float *__restrict__ xyz,
                                                            const float *__restrict__ center, int N, int G,
                                                            int k, int cpb, int64_t *__restrict__ nbr_idx,
-                                                           float *__restrict__ nbhd, float *__restrict__ ndist)
+                                                           float *__restrict__ nbhd, float *__restrict__ ndist,
+                                                           const int32_t *__restrict__ lengths)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     float4 *cloud = reinterpret_cast<float4 *>(smem);                                   // [N]
@@ -65,7 +77,8 @@ __global__ __launch_bounds__(W * 64) void knn_group_kernel(const float *__restri
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y;
-    stage_cloud(xyz + (size_t)b * N * 3, N, cloud);
+    const int n = cloud_rows<RAGGED>(lengths, b, N);
+    stage_cloud(xyz + (size_t)b * N * 3, n, cloud);
     __syncthreads();
 
     unsigned long long *list = lists + (size_t)w * KNN_CAP;
@@ -77,7 +90,7 @@ __global__ __launch_bounds__(W * 64) void knn_group_kernel(const float *__restri
 
         // pass 1: per-lane minimum key
         uint32_t umin = 0xFFFFFFFFu;
-        for (int i = lane; i < N; i += 64) {
+        for (int i = lane; i < n; i += 64) {
             const float4 pt = cloud[i];
             umin = ppt_umin(umin, float_order_key(expanded_sqdist_rn(qx, qy, qz, nq, pt.x, pt.y, pt.z, pt.w)));
         }
@@ -85,11 +98,11 @@ __global__ __launch_bounds__(W * 64) void knn_group_kernel(const float *__restri
 
         // pass 2: compact survivors
         int cnt = 0;
-        for (int base = 0; base < N; base += 64) {
+        for (int base = 0; base < n; base += 64) {
             const int i = base + lane;
             bool alive = false;
             uint32_t u = 0;
-            if (i < N) {
+            if (i < n) {
                 const float4 pt = cloud[i];
                 u = float_order_key(expanded_sqdist_rn(qx, qy, qz, nq, pt.x, pt.y, pt.z, pt.w));
                 alive = u <= Tb;
@@ -135,7 +148,7 @@ __global__ __launch_bounds__(W * 64) void knn_group_kernel(const float *__restri
             bool have_prev = false;
             for (int r = 0; r < k; ++r) {
                 uint32_t bhi = 0xFFFFFFFFu, blo = 0xFFFFFFFFu;
-                for (int i = lane; i < N; i += 64) {
+                for (int i = lane; i < n; i += 64) {
                     const float4 pt = cloud[i];
                     const uint32_t u = float_order_key(expanded_sqdist_rn(qx, qy, qz, nq, pt.x, pt.y, pt.z, pt.w));
                     const unsigned long long key = ((unsigned long long)u << 32) | (uint32_t)i;
@@ -160,24 +173,43 @@ __global__ __launch_bounds__(W * 64) void knn_group_kernel(const float *__restri
                 }
             }
         }
+        if (RAGGED && k > n) {
+            // a ragged cloud shorter than k (the caller's precondition, which the host cannot check): memory safety only, no
+            // reference semantic -- n < k <= 64, so the list holds all n keys and slots 0 .. n-1 are written; the rest repeat
+            // slot 0's neighbour (the ball query's pad-with-first)
+            unsigned long long m0 = ~0ull;
+            for (int f = 0; f < cnt; ++f) m0 = list[f] < m0 ? list[f] : m0;
+            const uint32_t i0 = (uint32_t)m0;
+            const float4 pt = cloud[i0];
+            for (int j = n + lane; j < k; j += 64) {
+                if (oi) oi[j] = (int64_t)i0;
+                if (od) od[j] = expanded_sqdist_rn(qx, qy, qz, nq, pt.x, pt.y, pt.z, pt.w);
+                if (on) {
+                    on[j * 3 + 0] = __fsub_rn(pt.x, qx);
+                    on[j * 3 + 1] = __fsub_rn(pt.y, qy);
+                    on[j * 3 + 2] = __fsub_rn(pt.z, qz);
+                }
+            }
+        }
         wave_lds_fence();   // the list is reused by this wave's next centre
     }
 }
 
 // Ball query: first K indices (ascending) with NOT(d > r^2); pad with the first hit
 // (pointnet2_utils.py:100-107).  Same staging; one wave per centre, 64 candidates per step.
-template <int W>
+template <int W, bool RAGGED>
 __global__ __launch_bounds__(W * 64) void ball_query_kernel(const float *__restrict__ xyz,
                                                             const float *__restrict__ center, int N, int S,
                                                             float r2, int K, int cpb, int64_t *__restrict__ idx,
-                                                            float *__restrict__ gxyz)
+                                                            float *__restrict__ gxyz, const int32_t *__restrict__ lengths)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     float4 *cloud = reinterpret_cast<float4 *>(smem);
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y;
-    stage_cloud(xyz + (size_t)b * N * 3, N, cloud);
+    const int n = cloud_rows<RAGGED>(lengths, b, N);
+    stage_cloud(xyz + (size_t)b * N * 3, n, cloud);
     __syncthreads();
     const int c_end = min(S, (int)(blockIdx.x + 1) * cpb);
     for (int c = blockIdx.x * cpb + w; c < c_end; c += W) {
@@ -186,11 +218,11 @@ __global__ __launch_bounds__(W * 64) void ball_query_kernel(const float *__restr
         const float nq = sqnorm3_rn(qx, qy, qz);
         int64_t *o = idx + ((size_t)b * S + c) * K;
         int cnt = 0;
-        int first = N;   // reference fill value when nothing is inside the ball
-        for (int base = 0; base < N && cnt < K; base += 64) {
+        int first = n;   // reference fill value when nothing is inside the ball: the cloud's own row count
+        for (int base = 0; base < n && cnt < K; base += 64) {
             const int i = base + lane;
             bool hit = false;
-            if (i < N) {
+            if (i < n) {
                 const float4 pt = cloud[i];
                 hit = !(expanded_sqdist_rn(qx, qy, qz, nq, pt.x, pt.y, pt.z, pt.w) > r2);
             }
@@ -212,7 +244,7 @@ __global__ __launch_bounds__(W * 64) void ball_query_kernel(const float *__restr
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             float *g = gxyz + ((size_t)b * S + c) * K * 3;
             for (int j = lane; j < K; j += 64) {
-                const int i = min((int)o[j], N - 1);
+                const int i = min((int)o[j], n - 1);
                 const float4 pt = cloud[i];
                 g[j * 3 + 0] = __fsub_rn(pt.x, qx); g[j * 3 + 1] = __fsub_rn(pt.y, qy); g[j * 3 + 2] = __fsub_rn(pt.z, qz);
             }
@@ -225,16 +257,17 @@ __global__ __launch_bounds__(W * 64) void ball_query_kernel(const float *__restr
 // against all radii (the reference evaluates square_distance once per radius, :99; three launches of ball_query_kernel staged
 // the 128 KB of an 8192-point cloud three times and walked it three times).  Hits write the index AND the centred
 // coordinates at once (no read-back of the index list); a list is padded from the first hit, which is kept in a register.
-template <int W, int NR>
+template <int W, int NR, bool RAGGED>
 __global__ __launch_bounds__(W * 64) void ball_query_multi_kernel(const float *__restrict__ xyz, const float *__restrict__ center, int N,
-                                                                  int S, int cpb, ppt_ball_multi q)
+                                                                  int S, int cpb, ppt_ball_multi q, const int32_t *__restrict__ lengths)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     float4 *cloud = reinterpret_cast<float4 *>(smem);
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y;
-    stage_cloud(xyz + (size_t)b * N * 3, N, cloud);
+    const int n = cloud_rows<RAGGED>(lengths, b, N);
+    stage_cloud(xyz + (size_t)b * N * 3, n, cloud);
     __syncthreads();
     const int c_end = min(S, (int)(blockIdx.x + 1) * cpb);
     for (int c = blockIdx.x * cpb + w; c < c_end; c += W) {
@@ -243,13 +276,13 @@ __global__ __launch_bounds__(W * 64) void ball_query_multi_kernel(const float *_
         const float nq = sqnorm3_rn(qx, qy, qz);
         int cnt[NR], first[NR];
 #pragma unroll
-        for (int j = 0; j < NR; ++j) { cnt[j] = 0; first[j] = N; }
+        for (int j = 0; j < NR; ++j) { cnt[j] = 0; first[j] = n; }
         bool more = true;
-        for (int base = 0; base < N && more; base += 64) {
+        for (int base = 0; base < n && more; base += 64) {
             const int i = base + lane;
             float d = INFINITY;
             float4 pt = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i < N) {
+            if (i < n) {
                 pt = cloud[i];
                 d = expanded_sqdist_rn(qx, qy, qz, nq, pt.x, pt.y, pt.z, pt.w);
             }
@@ -257,7 +290,7 @@ __global__ __launch_bounds__(W * 64) void ball_query_multi_kernel(const float *_
 #pragma unroll
             for (int j = 0; j < NR; ++j) {
                 if (j < q.n && cnt[j] < q.K[j]) {                          // (wave-uniform)
-                    const bool hit = i < N && !(d > q.r2[j]);
+                    const bool hit = i < n && !(d > q.r2[j]);
                     const unsigned long long mask = __ballot(hit);
                     if (mask) {
                         if (cnt[j] == 0) first[j] = base + (int)__builtin_ctzll(mask);
@@ -282,7 +315,7 @@ __global__ __launch_bounds__(W * 64) void ball_query_multi_kernel(const float *_
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
             if (j < q.n) {
-                const float4 pf = cloud[min(first[j], N - 1)];
+                const float4 pf = cloud[min(first[j], n - 1)];
                 for (int k = min(cnt[j], q.K[j]) + lane; k < q.K[j]; k += 64) {
                     const size_t o = ((size_t)b * S + c) * q.K[j] + k;
                     q.idx[j][o] = (int64_t)first[j];
@@ -325,6 +358,9 @@ __global__ __launch_bounds__(256) void square_distance_kernel(const float *__res
 
 }  // namespace
 
+// ---- entry points: the ragged forms (N read as Nmax, lengths [B] on the device) and today's share one launcher and one kernel
+// body each, instantiated with and without RAGGED
+
 extern "C" int ppt_square_distance_f32(const float *src, const float *dst, int B, int S, int N, float *out, void *stream)
 {
     if (!src || !dst || !out || B <= 0 || S <= 0 || N <= 0) return PPT_EINVAL;
@@ -335,25 +371,40 @@ extern "C" int ppt_square_distance_f32(const float *src, const float *dst, int B
     return PPT_OK;
 }
 
-extern "C" int ppt_ball_query_multi_f32(const float *xyz, const float *center, int B, int N, int S, const ppt_ball_multi *q, void *stream)
+template <bool RAGGED>
+static int ball_query_multi_launch(const float *xyz, const float *center, const int32_t *lengths, int B, int N, int S, const ppt_ball_multi *q,
+                                   void *stream)
 {
     if (!xyz || !center || !q || B <= 0 || N <= 0 || S <= 0 || N > 10240 || q->n < 1 || q->n > 3) return PPT_EINVAL;
     for (int j = 0; j < q->n; ++j)
         if (!q->idx[j] || q->K[j] <= 0) return PPT_EINVAL;
     constexpr int W = 8;
     const size_t lds = (size_t)N * 16;
-    static const hipError_t optin = hipFuncSetAttribute((const void *)ball_query_multi_kernel<W, 3>,
+    static const hipError_t optin = hipFuncSetAttribute((const void *)ball_query_multi_kernel<W, 3, RAGGED>,
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, 10240 * 16);
     if (lds > 64 * 1024 && optin != hipSuccess) return PPT_ELAUNCH;
     const int cpb = 32;
     dim3 grid((S + cpb - 1) / cpb, B);
-    hipLaunchKernelGGL((ball_query_multi_kernel<W, 3>), grid, dim3(W * 64), lds, ppt_stream(stream), xyz, center, N, S, cpb, *q);
+    hipLaunchKernelGGL((ball_query_multi_kernel<W, 3, RAGGED>), grid, dim3(W * 64), lds, ppt_stream(stream), xyz, center, N, S, cpb, *q, lengths);
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }
 
-extern "C" int ppt_knn_group_f32(const float *xyz, const float *center, int B, int N, int G, int k,
-                                 int64_t *nbr_idx, float *neighborhood, float *nbr_dist, void *stream)
+extern "C" int ppt_ball_query_multi_f32(const float *xyz, const float *center, int B, int N, int S, const ppt_ball_multi *q, void *stream)
+{
+    return ball_query_multi_launch<false>(xyz, center, nullptr, B, N, S, q, stream);
+}
+
+extern "C" int ppt_ball_query_multi_ragged_f32(const float *xyz, const float *center, int B, int Nmax, int S, const int32_t *lengths,
+                                               const ppt_ball_multi *q, void *stream)
+{
+    if (!lengths) return PPT_EINVAL;
+    return ball_query_multi_launch<true>(xyz, center, lengths, B, Nmax, S, q, stream);
+}
+
+template <bool RAGGED>
+static int knn_group_launch(const float *xyz, const float *center, const int32_t *lengths, int B, int N, int G, int k,
+                            int64_t *nbr_idx, float *neighborhood, float *nbr_dist, void *stream)
 {
     if (!xyz || !center || B <= 0 || N <= 0 || G <= 0 || k <= 0 || k > 64 || k > N || N > 8192)
         return PPT_EINVAL;
@@ -361,13 +412,44 @@ extern "C" int ppt_knn_group_f32(const float *xyz, const float *center, int B, i
     const size_t lds = (size_t)N * 16 + (size_t)W * KNN_CAP * 8;
     // the opt-in to > 64 KB of dynamic LDS is made ONCE per kernel (thread-safe static initialisation), for the
     // largest cloud the entry point accepts -- not on every launch
-    static const hipError_t optin = hipFuncSetAttribute((const void *)knn_group_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    static const hipError_t optin = hipFuncSetAttribute((const void *)knn_group_kernel<W, RAGGED>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                          8192 * 16 + W * KNN_CAP * 8);
     if (lds > 64 * 1024 && optin != hipSuccess) return PPT_ELAUNCH;
     const int cpb = 32;
     dim3 grid((G + cpb - 1) / cpb, B);
-    hipLaunchKernelGGL((knn_group_kernel<W>), grid, dim3(W * 64), lds, ppt_stream(stream), xyz, center, N, G, k,
-                       cpb, nbr_idx, neighborhood, nbr_dist);
+    hipLaunchKernelGGL((knn_group_kernel<W, RAGGED>), grid, dim3(W * 64), lds, ppt_stream(stream), xyz, center, N, G, k,
+                       cpb, nbr_idx, neighborhood, nbr_dist, lengths);
+    PPT_CHECK_LAUNCH();
+    return PPT_OK;
+}
+
+extern "C" int ppt_knn_group_f32(const float *xyz, const float *center, int B, int N, int G, int k,
+                                 int64_t *nbr_idx, float *neighborhood, float *nbr_dist, void *stream)
+{
+    return knn_group_launch<false>(xyz, center, nullptr, B, N, G, k, nbr_idx, neighborhood, nbr_dist, stream);
+}
+
+extern "C" int ppt_knn_group_ragged_f32(const float *xyz, const float *center, int B, int Nmax, int G, int k, const int32_t *lengths,
+                                        int64_t *nbr_idx, float *neighborhood, float *nbr_dist, void *stream)
+{
+    if (!lengths) return PPT_EINVAL;
+    return knn_group_launch<true>(xyz, center, lengths, B, Nmax, G, k, nbr_idx, neighborhood, nbr_dist, stream);
+}
+
+template <bool RAGGED>
+static int ball_query_launch(const float *xyz, const float *center, const int32_t *lengths, int B, int N, int S, float radius_sq,
+                             int K, int64_t *idx, float *grouped_xyz, void *stream)
+{
+    if (!xyz || !center || !idx || B <= 0 || N <= 0 || S <= 0 || K <= 0 || N > 10240) return PPT_EINVAL;
+    constexpr int W = 8;
+    const size_t lds = (size_t)N * 16;
+    static const hipError_t optin = hipFuncSetAttribute((const void *)ball_query_kernel<W, RAGGED>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                         10240 * 16);
+    if (lds > 64 * 1024 && optin != hipSuccess) return PPT_ELAUNCH;
+    const int cpb = 32;
+    dim3 grid((S + cpb - 1) / cpb, B);
+    hipLaunchKernelGGL((ball_query_kernel<W, RAGGED>), grid, dim3(W * 64), lds, ppt_stream(stream), xyz, center, N, S,
+                       radius_sq, K, cpb, idx, grouped_xyz, lengths);
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }
@@ -375,16 +457,12 @@ extern "C" int ppt_knn_group_f32(const float *xyz, const float *center, int B, i
 extern "C" int ppt_ball_query_f32(const float *xyz, const float *center, int B, int N, int S, float radius_sq,
                                   int K, int64_t *idx, float *grouped_xyz, void *stream)
 {
-    if (!xyz || !center || !idx || B <= 0 || N <= 0 || S <= 0 || K <= 0 || N > 10240) return PPT_EINVAL;
-    constexpr int W = 8;
-    const size_t lds = (size_t)N * 16;
-    static const hipError_t optin = hipFuncSetAttribute((const void *)ball_query_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                         10240 * 16);
-    if (lds > 64 * 1024 && optin != hipSuccess) return PPT_ELAUNCH;
-    const int cpb = 32;
-    dim3 grid((S + cpb - 1) / cpb, B);
-    hipLaunchKernelGGL((ball_query_kernel<W>), grid, dim3(W * 64), lds, ppt_stream(stream), xyz, center, N, S,
-                       radius_sq, K, cpb, idx, grouped_xyz);
-    PPT_CHECK_LAUNCH();
-    return PPT_OK;
+    return ball_query_launch<false>(xyz, center, nullptr, B, N, S, radius_sq, K, idx, grouped_xyz, stream);
+}
+
+extern "C" int ppt_ball_query_ragged_f32(const float *xyz, const float *center, int B, int Nmax, int S, float radius_sq, int K,
+                                         const int32_t *lengths, int64_t *idx, float *grouped_xyz, void *stream)
+{
+    if (!lengths) return PPT_EINVAL;
+    return ball_query_launch<true>(xyz, center, lengths, B, Nmax, S, radius_sq, K, idx, grouped_xyz, stream);
 }

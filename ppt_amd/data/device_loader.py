@@ -39,7 +39,12 @@ it is) and yields (pc, target).  Its row selection: FPS from a fresh randint(0, 
 npoints; otherwise the reference's random_sample, which shuffles ONE persistent arange(npoints) cumulatively -- in numpy mode the
 loader owns that array for its lifetime, as the reference's dataset object does; in device mode every (index, epoch) gets a fresh
 Philox permutation instead (a uniformly random order either way; the cumulative state is what a worker process would not share).
-Not covered: the rendered images, the captions and their random.choice, normals, clouds of differing length under FPS.
+Clouds of differing length under FPS (`ragged=True`, recipes "modelnet" and "shapenet55"): the batch still takes one draw launch,
+one FPS launch and one cloud_prep launch -- ppt_fps_ragged_f32 walks every cloud's own row count, and each cloud's rows are the ones a
+set of that length alone would give.  A "modelnet" cloud of exactly npoints rows keeps the reference's treatment (no FPS, the rows
+as stored, no randint drawn for it); "shapenet55" refuses a ragged set that holds one (it would need random_sample's persistent
+permutation for some rows of the batch and FPS for the others).
+Not covered: the rendered images, the captions and their random.choice, normals.
 """
 import collections
 import math
@@ -240,7 +245,7 @@ class DeviceBatchLoader:
     No stream is created here: see DevicePrefetcher._stream for what a further stream does to the two-stream schedule."""
 
     def __init__(self, cloud_set, batch_size, npoints, recipe, train, shuffle=True, drop_last=False, seed=0, draws="device", rank=0,
-                 world_size=1, ahead=2, use_height=False, augment=None):
+                 world_size=1, ahead=2, use_height=False, augment=None, ragged=False):
         if recipe not in RECIPES:
             raise ValueError(f"recipe must be one of {RECIPES}, got {recipe!r}")
         if draws not in ("device", "numpy"):
@@ -267,10 +272,20 @@ class DeviceBatchLoader:
         else:
             if rows.min() < self.npoints:
                 raise ValueError(f"recipe {recipe!r}: every cloud needs at least npoints = {self.npoints} rows (shortest: {rows.min()})")
-            if recipe in FPS_RECIPES and rows.min() != rows.max():
+            if recipe in FPS_RECIPES and rows.min() != rows.max() and not ragged:
                 raise ValueError(f"recipe {recipe!r}: the batched FPS launch walks one row count for all its clouds; give clouds of one "
-                                 "length (ModelNet's are), e.g. one DeviceCloudSet per length")
-        self._fps_rows = int(rows[0]) if recipe in FPS_RECIPES and rows[0] > self.npoints else 0
+                                 "length (ModelNet's are), e.g. one DeviceCloudSet per length, or pass ragged=True (one FPS launch "
+                                 "that takes every cloud's own length)")
+        # ragged: the set's lengths differ and the FPS launch takes them (ops.fps(lengths=)); a uniform set is today's path
+        self._ragged = bool(ragged) and recipe in FPS_RECIPES and rows.min() != rows.max()
+        self._exact = self._ragged and bool((rows == self.npoints).any())     # clouds of exactly npoints rows: no FPS for those
+        if self._exact and recipe == "shapenet55":
+            raise ValueError(f"recipe 'shapenet55', ragged: a cloud of exactly npoints = {self.npoints} rows takes random_sample's "
+                             "persistent permutation, not FPS; keep such clouds in a set of their own")
+        if self._ragged:
+            self._fps_rows = int(rows.max())
+        else:
+            self._fps_rows = int(rows[0]) if recipe in FPS_RECIPES and rows[0] > self.npoints else 0
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -311,8 +326,8 @@ class DeviceBatchLoader:
         rows = self.set.rows(idx)
         per = [numpy_draws(rs, self.recipe, self.train, int(r), n, self.augment, self._permutation) for r in rows]
         parts = {}
-        if "start" in per[0]:
-            parts["start"] = np.asarray([d["start"] for d in per], dtype=np.int64)
+        if any("start" in d for d in per):                # (ragged: a cloud of exactly npoints rows draws none and is not sampled)
+            parts["start"] = np.asarray([d.get("start", 0) for d in per], dtype=np.int64)
         if "scale" in per[0]:
             parts["scale"] = np.stack([d["scale"] for d in per]).astype(np.float64)
             parts["shift"] = np.stack([d["shift"] for d in per]).astype(np.float64)
@@ -362,7 +377,16 @@ class DeviceBatchLoader:
             xyz = s.points.index_select(0, item)
             if xyz.shape[1] != self._fps_rows or xyz.shape[2] != 3:
                 xyz = xyz[:, :self._fps_rows, :3].contiguous()
-            sel, _ = ops.fps(xyz, n, d["start"])
+            if self._ragged:
+                lens = s.lengths.index_select(0, item)
+                start = d.get("start")    # numpy draws, a batch made of npoints-row clouds only: none of them drew a start
+                if start is None:
+                    start = torch.zeros(len(idx), dtype=torch.int64, device=xyz.device)
+                sel, _ = ops.fps(xyz, n, start, lengths=lens)
+                if self._exact:           # dataset_3d.py:300-303: a cloud of npoints rows is taken as stored
+                    sel = torch.where((lens == n).unsqueeze(1), torch.arange(n, device=sel.device).unsqueeze(0), sel)
+            else:
+                sel, _ = ops.fps(xyz, n, d["start"])
         out = ops.cloud_prep(s.points, item, n, sel=sel, lengths=s.lengths, normalize=self.recipe in FPS_RECIPES, scale=d.get("scale"),
                              shift=d.get("shift"), perm=d.get("perm"), seg_src=s.seg if part else None)
         target = s.labels.index_select(0, item)

@@ -15,6 +15,7 @@ Reference citations are relative to the upstream repo.
 import collections
 import os
 
+import numpy as np
 import torch
 
 from . import ops
@@ -149,10 +150,34 @@ def _bn_params(sd, p):
 # =================================================================================================
 # point branch
 # =================================================================================================
-def group_points(pc, num_group, group_size, fps_start):
-    """Group.forward (dvae.py:159-181): FPS centres + kNN neighbourhoods (centre-subtracted)."""
-    _, center = ops.fps(pc, num_group, fps_start)
-    _, nbhd = ops.knn_group(pc, center, group_size, want_idx=False)
+def cloud_lengths(lengths, B, Nmax, device, least=1, what="lengths"):
+    """The per-cloud row counts of a padded batch [B, Nmax, 3] as the index kernels take them: [B] int32 on `device`.
+    A host sequence / numpy array is validated (B entries, max(1, least) <= length <= Nmax) and uploaded; a device int32 tensor is
+    the caller's promise of the same and costs no host read (only its shape and dtype are looked at)."""
+    if torch.is_tensor(lengths) and lengths.is_cuda:
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
+            raise ValueError(f"{what}: a device tensor must be int32 of shape ({B},), got {lengths.dtype} {tuple(lengths.shape)}")
+        return lengths.to(device).contiguous()
+    host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths)
+    if host.ndim != 1 or host.shape[0] != B or host.dtype.kind not in "iu":
+        raise ValueError(f"{what}: expected {B} integers (one row count per cloud), got shape {host.shape} dtype {host.dtype}")
+    lo = max(1, int(least))
+    if host.min() < lo or host.max() > Nmax:
+        raise ValueError(f"{what}: every cloud needs {lo} <= length <= Nmax = {Nmax} rows (got {int(host.min())} .. {int(host.max())})")
+    return torch.from_numpy(host.astype(np.int32)).to(device)
+
+
+def ragged_fps_start(lengths):
+    """misc.py:59's randint(0, N) for clouds of differing length: (rand(B) * lengths).long(), clamped below each length."""
+    u = torch.rand(lengths.shape[0], device=lengths.device)
+    return torch.minimum((u * lengths).long(), lengths.long() - 1)
+
+
+def group_points(pc, num_group, group_size, fps_start, lengths=None):
+    """Group.forward (dvae.py:159-181): FPS centres + kNN neighbourhoods (centre-subtracted).  lengths [B] i32 (device): cloud b is
+    the first lengths[b] rows of pc[b]; the result has the same fixed shape, so everything behind it runs unchanged."""
+    _, center = ops.fps(pc, num_group, fps_start, lengths=lengths)
+    _, nbhd = ops.knn_group(pc, center, group_size, want_idx=False, lengths=lengths)
     return nbhd, center
 
 
@@ -530,27 +555,29 @@ def _sa_msg_level(sd, p, wc, cfg, xyz, feats, start, train, upd, pre=None):
     return _sa_level(sd, branches, wc, cfg["npoint"], xyz, feats, start, train, upd, xyz_first=False, pre=pre)
 
 
-def _sa_group(xyz, npoint, branches, start, first):
+def _sa_group(xyz, npoint, branches, start, first, lengths=None):
     """The part of a set-abstraction level that depends on coordinates only: FPS + one ball query per branch.
-    -> [new_xyz [B,S,3], per branch: grouped centred xyz [B,S,K,3] (first level) or neighbour indices [B,S,K]]."""
-    _, new_xyz = ops.fps(xyz, npoint, start)
+    -> [new_xyz [B,S,3], per branch: grouped centred xyz [B,S,K,3] (first level) or neighbour indices [B,S,K]].
+    lengths [B] i32 (device): per-cloud row counts of xyz (the input cloud, level 1)."""
+    _, new_xyz = ops.fps(xyz, npoint, start, lengths=lengths)
     out = [new_xyz]
     if 1 < len(branches) <= 3:          # the scales of an MSG level share their centres: one pass over the cloud for all radii
-        for idx, gxyz in ops.ball_query_multi(xyz, new_xyz, list(branches), want_grouped=first):
+        for idx, gxyz in ops.ball_query_multi(xyz, new_xyz, list(branches), want_grouped=first, lengths=lengths):
             out.append(gxyz if first else idx)
         return out
     for r, K in branches:
-        idx, gxyz = ops.ball_query(xyz, new_xyz, r, K, want_grouped=True)
+        idx, gxyz = ops.ball_query(xyz, new_xyz, r, K, want_grouped=True, lengths=lengths)
         out.append(gxyz if first else idx)
     return out
 
 
-def pointnet2_group(pc, fps_starts, levels):
+def pointnet2_group(pc, fps_starts, levels, lengths=None):
     """Grouping stage of Pointnet2_Msg / Pointnet2_Ssg (both levels): levels = [(npoint, [(radius, K), ...]), ...].
-    A function of the input cloud and the FPS starts alone, so a trainer may run it ahead of the step."""
+    A function of the input cloud and the FPS starts alone, so a trainer may run it ahead of the step.
+    lengths [B] i32 (device): per-cloud row counts of pc; they matter at level 1 only (level 2 runs on level 1's fixed centres)."""
     out, xyz = [], pc
     for li, ((npoint, branches), start) in enumerate(zip(levels, fps_starts)):
-        g = _sa_group(xyz.contiguous(), npoint, branches, start, first=li == 0)
+        g = _sa_group(xyz.contiguous(), npoint, branches, start, first=li == 0, lengths=lengths if li == 0 else None)
         out += g
         xyz = g[0]
     return out

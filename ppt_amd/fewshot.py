@@ -41,8 +41,11 @@ def run_fewshot(model, train_set, test_set, args, trainer=None):
     if recipe not in ("modelnet", "scanobjectnn"):
         raise ValueError(f"run_fewshot: recipe must be 'modelnet' or 'scanobjectnn', got {recipe!r}")
     epochs, batch_size, npoints, seed = (int(_arg(args, k)) for k in ("epochs", "batch_size", "npoints", "seed"))
-    train_loader = DeviceBatchLoader(train_set, batch_size, npoints, recipe, train=True, shuffle=True, drop_last=False, seed=seed)
-    test_loader = DeviceBatchLoader(test_set, batch_size, npoints, recipe, train=False, shuffle=False, drop_last=False, seed=seed)
+    # (ragged: a set that carries lengths may hold clouds of differing length; the loader's one FPS launch then takes them)
+    train_loader = DeviceBatchLoader(train_set, batch_size, npoints, recipe, train=True, shuffle=True, drop_last=False, seed=seed,
+                                     ragged=train_set.lengths is not None)
+    test_loader = DeviceBatchLoader(test_set, batch_size, npoints, recipe, train=False, shuffle=False, drop_last=False, seed=seed,
+                                    ragged=test_set.lengths is not None)
     smoothing = float(_arg(args, "label_smoothing"))
     criterion = torch.nn.CrossEntropyLoss(label_smoothing=smoothing)                      # main_fewshot.py:52
     if trainer is None:

@@ -883,12 +883,15 @@ class ULIP_WITH_IMAGE(nn.Module):
             return 0
         return cand if bool((prompts[:, :cand] == prompts[:1, :cand]).all().item()) else 0
 
-    def encode_pc(self, pc, cls_label=None):
-        """ULIP_models.py:250-258."""
+    def encode_pc(self, pc, cls_label=None, lengths=None):
+        """ULIP_models.py:250-258.  lengths: a row count per cloud of a padded batch (recognition with PointBERT or PointNet++; the
+        encoder validates it: PointTransformer.forward) -- every other encoder and part-seg raise ValueError."""
         if self.task == 'partseg':
+            if lengths is not None:
+                raise ValueError("part-seg takes no ragged input (lengths=): the decoder works over all B*N input rows")
             pc_feat = self.point_encoder(pc, cls_label)
         else:
-            pc_feat = self.point_encoder(pc)
+            pc_feat = self.point_encoder(pc) if lengths is None else self.point_encoder(pc, lengths=lengths)
         wt = engine._f32_cache(self._cache()).get(self.pc_projection, "wt")     # [embed, feat]
         lead = pc_feat.shape[:-1]
         return matmul_nt(pc_feat.reshape(-1, pc_feat.shape[-1]), wt, self._head_precision()).view(*lead, -1)
@@ -980,15 +983,17 @@ class ULIP_WITH_IMAGE(nn.Module):
             self._text_stream = graphs.shared_text_stream()
         return self._text_stream
 
-    def forward(self, pc, cls_label=None):
-        """ULIP_models.py:260-283 -> logits [B,C] (partseg: [B,N,C])."""
+    def forward(self, pc, cls_label=None, lengths=None):
+        """ULIP_models.py:260-283 -> logits [B,C] (partseg: [B,N,C]).  lengths: see encode_pc."""
         # the rows the caller's criterion will average over: fixes the power-of-two scale of every 16-bit backward stage created
         # by this forward (ppt_amd/gradscale.py) -- a plain `loss.backward()` (main_cls.py:197, main_partseg.py:214) is then
         # scaled and un-scaled inside the nodes
+        if lengths is not None and self.task == 'partseg':
+            raise ValueError("part-seg takes no ragged input (lengths=): the decoder works over all B*N input rows")
         with gradscale.rows(pc.shape[0] * (pc.shape[1] if self.task == 'partseg' else 1)):
-            return self._forward(pc, cls_label)
+            return self._forward(pc, cls_label, lengths)
 
-    def _forward(self, pc, cls_label=None):
+    def _forward(self, pc, cls_label=None, lengths=None):
         cur = torch.cuda.current_stream()
         side = None
         if self.overlap_text_tower and pc.is_cuda:
@@ -997,7 +1002,7 @@ class ULIP_WITH_IMAGE(nn.Module):
             with torch.cuda.stream(side):
                 text_embed = self._text_embed()
         pe = self.point_encoder
-        ahead = ((self.eval_inputs_ready or graphs.ready_event(pc) is not None) and not self.training and not torch.is_grad_enabled() and pc.is_cuda
+        ahead = (lengths is None and (self.eval_inputs_ready or graphs.ready_event(pc) is not None) and not self.training and not torch.is_grad_enabled() and pc.is_cuda
                  and hasattr(pe, "group_ahead") and self.task != 'partseg')
         if ahead:
             # validate() with resident inputs (eval_inputs_ready): the next batch's FPS + kNN + tokenizer on the grouping stream,
@@ -1006,7 +1011,7 @@ class ULIP_WITH_IMAGE(nn.Module):
             pe.inputs_vouched = bool(self.eval_inputs_ready)     # (else: only tensors that carry their copy event run ahead)
         try:
             with self._tower_room():
-                pc_embed = self.encode_pc(pc, cls_label) if self.task == 'partseg' else self.encode_pc(pc)
+                pc_embed = self.encode_pc(pc, cls_label, lengths) if self.task == 'partseg' else self.encode_pc(pc, lengths=lengths)
         finally:
             if ahead:
                 pe.group_ahead = None
@@ -1027,10 +1032,13 @@ class ULIP_WITH_IMAGE(nn.Module):
             logits = matmul_nt((logit_scale * pc_embed).reshape(-1, pc_embed.shape[-1]), text_embed, hp)
         return logits.view(*lead, -1)
 
-    def forward_loss(self, pc, labels, smoothing):
-        """forward + CrossEntropyLoss(label_smoothing) for the case where nothing on the point side trains (head_type 0):
+    def forward_loss(self, pc, labels, smoothing, lengths=None):
+        """(lengths: refused with ValueError -- its fused head node is graph-replayed; use forward(pc, lengths=...) and a criterion.)
+        forward + CrossEntropyLoss(label_smoothing) for the case where nothing on the point side trains (head_type 0):
         same two-stream schedule as forward(), but everything between the towers is one fused, graph-replayed node
         (_HeadLossFn) instead of ~25 autograd-tracked launches.  -> (loss, logits)."""
+        if lengths is not None:
+            raise ValueError("forward_loss takes no lengths: run a ragged batch through forward(pc, lengths=...) and a criterion")
         with gradscale.rows(pc.shape[0]):
             return self._forward_loss(pc, labels, smoothing)
 

@@ -28,9 +28,15 @@ class Group(nn.Module):
         self.num_group = num_group
         self.group_size = group_size
 
-    def forward(self, xyz, start_idx=None):
-        """xyz [B,N,3] -> (neighborhood [B,G,M,3] centre-subtracted, center [B,G,3])."""
+    def forward(self, xyz, start_idx=None, lengths=None):
+        """xyz [B,N,3] -> (neighborhood [B,G,M,3] centre-subtracted, center [B,G,3]).  lengths: a row count per cloud (host
+        sequence, validated: group_size <= length <= N; or a device int32 tensor, taken on trust): cloud b is xyz[b, :lengths[b]]."""
         xyz = xyz.contiguous().float()
+        if lengths is not None:
+            lengths = engine.cloud_lengths(lengths, xyz.shape[0], xyz.shape[1], xyz.device, least=self.group_size)
+            start = engine.ragged_fps_start(lengths) if start_idx is None else start_idx.to(xyz.device).contiguous()
+            neighborhood, center = engine.group_points(xyz, self.num_group, self.group_size, start, lengths=lengths)
+            return neighborhood, center
         center = misc.fps(xyz, self.num_group, start_idx)
         idx, neighborhood = ops.knn_group(xyz, center, self.group_size)
         assert idx.size(1) == self.num_group

@@ -160,9 +160,21 @@ class _PointEncoderFn(torch.autograd.Function):
     """feat = PointTransformer(pc); gradients only for the un-frozen last-block parameters."""
 
     @staticmethod
-    def forward(ctx, module, pc, fps_start, dp, tier, names, *params):
+    def forward(ctx, module, pc, fps_start, dp, tier, names, lengths, *params):
         sd, cache, cfg, train = module._live_state(), module._cache(), module._cfg(), module.training
         ctx.module, ctx.tier, ctx.names = module, tier, names
+        if lengths is not None:
+            # ragged clouds: the grouping stage takes the lengths, everything behind it has its fixed shape.  Plain eager: no graph,
+            # no ahead stage (a graph would bake the lengths' pointer in, and the stage is keyed by the cloud's shape alone).
+            ctx.grad_scale = gradscale.current(engine._stage_wc(cache, "last_block").dtype, default_rows=pc.shape[0]) if tier > 0 else 1.0
+            gate, module.param_gate = module.param_gate, None
+            if gate is not None and pc.is_cuda:
+                torch.cuda.current_stream().wait_event(gate)
+            if fps_start is None:
+                fps_start, dp = engine.ragged_fps_start(lengths), module._draw_drop_path(pc.shape[0], pc.device)
+            grouped = engine.group_points(pc, cfg["num_group"], cfg["group_size"], fps_start, lengths=lengths)
+            feat, ctx.saved = engine.point_encoder_forward(sd, "", cache, None, None, dp, train, tier, cfg, grouped=grouped)
+            return feat
         # the power-of-two scale of the last block's 16-bit backward, fixed now (ppt_amd/gradscale.py; a bare PointTransformer
         # under its own criterion: the batch size)
         ctx.grad_scale = gradscale.current(engine._stage_wc(cache, "last_block").dtype, default_rows=pc.shape[0]) if tier > 0 else 1.0
@@ -288,7 +300,7 @@ class _PointEncoderFn(torch.autograd.Function):
         for n in ctx.names:
             g = grads[n]
             out.append(g.view_as(m._live_state()[n]))
-        return (None, None, None, None, None, None) + tuple(out)
+        return (None, None, None, None, None, None, None) + tuple(out)
 
 
 class PointTransformer(nn.Module):
@@ -450,16 +462,23 @@ class PointTransformer(nn.Module):
     # ---- reference API ---------------------------------------------------------------------
     load_model_from_ckpt = _load_model_from_ckpt
 
-    def forward(self, pts):
-        """pts [B,N,3] -> cat(cls, max) features [B, 2*trans_dim] (point_encoder.py:234-257)."""
+    def forward(self, pts, lengths=None):
+        """pts [B,N,3] -> cat(cls, max) features [B, 2*trans_dim] (point_encoder.py:234-257).
+        lengths: a row count per cloud for a padded batch of clouds of differing length -- a host sequence / numpy array (validated:
+        group_size <= length <= N, then uploaded) or a device int32 tensor [B] (the caller's promise; no host read).  Cloud b is
+        pts[b, :lengths[b]]; rows behind it are never read.  FPS and kNN take the lengths, the tower behind them is unchanged and
+        runs eagerly (no hipGraph, no ahead stage); the FPS start is drawn below each length unless `fps_start` is injected."""
         pts = pts.contiguous().float()
         B, N, _ = pts.shape
+        if lengths is not None:
+            lengths = engine.cloud_lengths(lengths, B, N, pts.device, least=self.group_size)
         if self.fps_start is None and self.drop_path_factors is None:
             start = dp = None                    # both draws happen inside _PointEncoderFn (and inside its hipGraph)
         else:
             start = self.fps_start
-            if start is None:
-                start = torch.randint(0, N, (B,), dtype=torch.long, device=pts.device)   # misc.py:59
+            if start is None:                    # misc.py:59
+                start = (torch.randint(0, N, (B,), dtype=torch.long, device=pts.device) if lengths is None
+                         else engine.ragged_fps_start(lengths))
             start = start.to(pts.device).contiguous()
             dp = self._draw_drop_path(B, pts.device)
         tier = self._tier() if torch.is_grad_enabled() else 0
@@ -468,7 +487,7 @@ class PointTransformer(nn.Module):
             if tier >= t:
                 names += [f"blocks.blocks.{self.depth - 1}.{n}" for n in TIER_PARAMS[t]]
         sd = self._live_state()
-        return _PointEncoderFn.apply(self, pts, start, dp, tier, names, *[sd[n] for n in names])
+        return _PointEncoderFn.apply(self, pts, start, dp, tier, names, lengths, *[sd[n] for n in names])
 
 
 class PointTransformer_partseg(nn.Module):
@@ -565,8 +584,10 @@ class PointTransformer_partseg(nn.Module):
 
     load_model_from_ckpt = _load_model_from_ckpt
 
-    def forward(self, pts, cls_label):
-
+    def forward(self, pts, cls_label, lengths=None):
+        if lengths is not None:
+            raise ValueError("PointTransformer_partseg: no ragged input (lengths=): its decoder convolves and batch-normalises over "
+                             "all B*N input rows, so padding rows would enter the statistics")
         from ...autograd import conv_bn_relu_rows
         pts = pts.contiguous().float()
         B, N, _ = pts.shape

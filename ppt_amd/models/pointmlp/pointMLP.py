@@ -143,7 +143,10 @@ class Model(nn.Module):
             print("unexpected keys:", incompatible.unexpected_keys)
         print("finished loading ckpt from {}".format(ckpt_path))
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        if lengths is not None:
+            raise ValueError("PointMLP: no ragged input (lengths=): the embedding convolves and batch-normalises over all B*N input "
+                             "rows, so padding rows would enter the statistics")
         xyz = x.contiguous().float()
         B, N, _ = xyz.shape
         cfg = self._cfg

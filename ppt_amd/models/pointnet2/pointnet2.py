@@ -50,7 +50,10 @@ class Pointnet2_Msg(nn.Module):
     """pointnet2.py:40-73.  forward(xyz [B,N,3]) -> [B,256].
 
     Build-specific knobs: `precision` (bf16 / fp32 parity), `fps_start` = (start1 [B], start2 [B]) and
-    `dropout_masks` = (m1 [B,512], m2 [B,256]) to inject the three RNG draws of the path in parity tests."""
+    `dropout_masks` = (m1 [B,512], m2 [B,256]) to inject the three RNG draws of the path in parity tests.
+    forward(xyz, lengths=...): a padded batch of clouds of differing length -- a host sequence / numpy array of row counts (validated:
+    1 <= length <= N, then uploaded) or a device int32 tensor [B] (the caller's promise).  Level 1's FPS and ball queries take the
+    lengths; the rest runs unchanged on its fixed shapes, eagerly (no hipGraph, no ahead stage)."""
     _engine_forward = staticmethod(engine.pointnet2_msg_forward)
     _group_levels = engine.PN2_MSG_LEVELS
     _graph_tag = "pn2_msg"
@@ -96,15 +99,18 @@ class Pointnet2_Msg(nn.Module):
             self._graphs.clear()
         return super().load_state_dict(*a, **k)
 
-    def forward(self, xyz):
+    def forward(self, xyz, lengths=None):
         xyz = xyz.contiguous().float()
         B, N, _ = xyz.shape
+        if lengths is not None:
+            lengths = engine.cloud_lengths(lengths, B, N, xyz.device)
         if self._wc is None or self._wc.dtype != self.precision:
             self._wc = engine.WeightCache(self.precision)
         if self.fps_start is not None:
             starts = tuple(s.to(xyz.device).contiguous() for s in self.fps_start)
         else:
-            starts = (torch.randint(0, N, (B,), dtype=torch.long, device=xyz.device),
+            starts = (torch.randint(0, N, (B,), dtype=torch.long, device=xyz.device) if lengths is None
+                      else engine.ragged_fps_start(lengths),
                       torch.randint(0, 512, (B,), dtype=torch.long, device=xyz.device))
         masks = None
         if self.dropout_masks is not None:
@@ -120,6 +126,9 @@ class Pointnet2_Msg(nn.Module):
             # ~90 shape-static launches: replayed from a hipGraph after graphs.WARMUP_CALLS eager calls (ppt_amd/graphs.py)
             key = (self._graph_tag, tuple(xyz.shape), masks is not None, train, wc.dtype)
             fwd = self._engine_forward
+            if lengths is not None:
+                grouped = engine.pointnet2_group(xyz, starts, self._group_levels, lengths=lengths)
+                return fwd(sd, "", wc, None, None, train, masks, grouped=grouped)
             if xyz.is_cuda and self.use_hip_graphs and ops.profiler is None and self._graphs.ready(key):
                 if self.group_ahead is not None:
                     # FPS + ball queries of both levels on the grouping stream (graphs.AheadStage), the rest from here

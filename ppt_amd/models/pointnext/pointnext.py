@@ -101,7 +101,10 @@ class BaseCls(nn.Module):
             return torch.float16
         return self.precision
 
-    def forward(self, pc):
+    def forward(self, pc, lengths=None):
+        if lengths is not None:
+            raise ValueError("PointNEXT: no ragged input (lengths=): the stem convolves and batch-normalises over all B*N input rows, "
+                             "so padding rows would enter the statistics")
         if pc.dim() != 3 or pc.shape[-1] != IN_CHANNELS:
             raise ValueError(f"PointNEXT expects [B, N, 4] clouds (x, y, z, height): build the batches with use_height "
                              f"(--use_height; DeviceBatchLoader(..., use_height=True)), got {tuple(pc.shape)}")

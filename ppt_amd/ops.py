@@ -104,22 +104,36 @@ def aligned16(t):
 
 
 # ---------------------------------------------------------------------------------------------
-def fps(xyz, M, start):
-    """H1.  xyz [B,N,3] f32, start [B] i64 -> (idx [B,M] i64, center [B,M,3] f32)."""
+def _chk_lengths(lengths, B):
+    """lengths of the ragged index kernels: [B] int32 on the device (cloud b = rows 0 .. lengths[b]-1 of its [Nmax, 3] slab)."""
+    _chk(lengths, torch.int32, "lengths")
+    if tuple(lengths.shape) != (B,):
+        raise RuntimeError(f"lengths: expected shape ({B},), got {tuple(lengths.shape)}")
+
+
+def fps(xyz, M, start, lengths=None):
+    """H1.  xyz [B,N,3] f32, start [B] i64 -> (idx [B,M] i64, center [B,M,3] f32).  lengths [B] i32 (device): cloud b is its first
+    lengths[b] rows, N is the row stride (ppt_fps_ragged_f32); each cloud's picks are those of that cloud alone."""
     _chk(xyz, torch.float32, "xyz"); _chk(start, torch.int64, "start")
     B, N, _ = xyz.shape
     idx = torch.empty((B, M), dtype=torch.int64, device=xyz.device)
     ctr = torch.empty((B, M, 3), dtype=torch.float32, device=xyz.device)
     if profiler is not None:
         profiler.begin("fps", float(B) * (12 * N + 8 * M))          # algorithmic HBM bytes (SURVEY §8(d))
-    _lib.check(_lib.lib().ppt_fps_f32(_p(xyz), B, N, M, _p(start), _p(idx), _p(ctr), _stream()), "ppt_fps_f32")
+    if lengths is None:
+        _lib.check(_lib.lib().ppt_fps_f32(_p(xyz), B, N, M, _p(start), _p(idx), _p(ctr), _stream()), "ppt_fps_f32")
+    else:
+        _chk_lengths(lengths, B)
+        _lib.check(_lib.lib().ppt_fps_ragged_f32(_p(xyz), B, N, M, _p(start), _p(lengths), _p(idx), _p(ctr), _stream()),
+                   "ppt_fps_ragged_f32")
     if profiler is not None:
         profiler.end()
     return idx, ctr
 
 
-def knn_group(xyz, center, k, want_idx=True, want_nbhd=True, want_dist=False):
-    """H2.  xyz [B,N,3], center [B,G,3] -> (nbr_idx [B,G,k] i64, neighborhood [B,G,k,3] f32[, dist [B,G,k] f32])."""
+def knn_group(xyz, center, k, want_idx=True, want_nbhd=True, want_dist=False, lengths=None):
+    """H2.  xyz [B,N,3], center [B,G,3] -> (nbr_idx [B,G,k] i64, neighborhood [B,G,k,3] f32[, dist [B,G,k] f32]).
+    lengths [B] i32 (device): per-cloud row counts, every one >= k (ppt_knn_group_ragged_f32)."""
     _chk(xyz, torch.float32, "xyz"); _chk(center, torch.float32, "center")
     B, N, _ = xyz.shape
     G = center.shape[1]
@@ -128,16 +142,21 @@ def knn_group(xyz, center, k, want_idx=True, want_nbhd=True, want_dist=False):
     if profiler is not None:
         profiler.begin("knn_group", float(B) * (12 * N + 12 * G + 8 * G * k + 12 * G * k))
     nd = torch.empty((B, G, k), dtype=torch.float32, device=xyz.device) if want_dist else None
-    _lib.check(_lib.lib().ppt_knn_group_f32(_p(xyz), _p(center), B, N, G, k, _p(idx), _p(nb), _p(nd), _stream()),
-               "ppt_knn_group_f32")
+    if lengths is None:
+        _lib.check(_lib.lib().ppt_knn_group_f32(_p(xyz), _p(center), B, N, G, k, _p(idx), _p(nb), _p(nd), _stream()),
+                   "ppt_knn_group_f32")
+    else:
+        _chk_lengths(lengths, B)
+        _lib.check(_lib.lib().ppt_knn_group_ragged_f32(_p(xyz), _p(center), B, N, G, k, _p(lengths), _p(idx), _p(nb), _p(nd),
+                                                       _stream()), "ppt_knn_group_ragged_f32")
     if profiler is not None:
         profiler.end()
     return (idx, nb, nd) if want_dist else (idx, nb)
 
 
-def ball_query_multi(xyz, center, queries, want_grouped=False):
+def ball_query_multi(xyz, center, queries, want_grouped=False, lengths=None):
     """queries = [(radius, K), ...] (1..3) around the same centres, one pass over the cloud (ppt_ball_query_multi_f32)
-    -> [(idx [B,S,K] i64, grouped_xyz [B,S,K,3] | None), ...]; same results as ball_query per pair."""
+    -> [(idx [B,S,K] i64, grouped_xyz [B,S,K,3] | None), ...]; same results as ball_query per pair.  lengths: as ball_query."""
     _chk(xyz, torch.float32, "xyz"); _chk(center, torch.float32, "center")
     import numpy as np
     B, N, _ = xyz.shape
@@ -154,7 +173,12 @@ def ball_query_multi(xyz, center, queries, want_grouped=False):
         bytes_ += 8 * S * K + (12 * S * K if want_grouped else 0)
     if profiler is not None:
         profiler.begin("ball_query", float(B) * bytes_)
-    _lib.check(_lib.lib().ppt_ball_query_multi_f32(_p(xyz), _p(center), B, N, S, ctypes.byref(q), _stream()), "ppt_ball_query_multi_f32")
+    if lengths is None:
+        _lib.check(_lib.lib().ppt_ball_query_multi_f32(_p(xyz), _p(center), B, N, S, ctypes.byref(q), _stream()), "ppt_ball_query_multi_f32")
+    else:
+        _chk_lengths(lengths, B)
+        _lib.check(_lib.lib().ppt_ball_query_multi_ragged_f32(_p(xyz), _p(center), B, N, S, _p(lengths), ctypes.byref(q), _stream()),
+                   "ppt_ball_query_multi_ragged_f32")
     if profiler is not None:
         profiler.end()
     return outs
@@ -170,8 +194,9 @@ def square_distance(src, dst):
     return out
 
 
-def ball_query(xyz, center, radius, K, want_grouped=False):
-    """H7.  -> idx [B,S,K] i64 (query_ball_point semantics) [, grouped_xyz [B,S,K,3] = xyz[idx] - center]."""
+def ball_query(xyz, center, radius, K, want_grouped=False, lengths=None):
+    """H7.  -> idx [B,S,K] i64 (query_ball_point semantics) [, grouped_xyz [B,S,K,3] = xyz[idx] - center].  lengths [B] i32
+    (device): per-cloud row counts; an empty ball is filled with the cloud's own length (ppt_ball_query_ragged_f32)."""
     _chk(xyz, torch.float32, "xyz"); _chk(center, torch.float32, "center")
     B, N, _ = xyz.shape
     S = center.shape[1]
@@ -181,8 +206,13 @@ def ball_query(xyz, center, radius, K, want_grouped=False):
     g = torch.empty((B, S, K, 3), dtype=torch.float32, device=xyz.device) if want_grouped else None
     if profiler is not None:                    # algorithmic HBM bytes per SA branch: cloud + centres + indices (+ grouped xyz)
         profiler.begin("ball_query", float(B) * (12 * N + 12 * S + 8 * S * K + (12 * S * K if want_grouped else 0)))
-    _lib.check(_lib.lib().ppt_ball_query_f32(_p(xyz), _p(center), B, N, S, r2, K, _p(idx), _p(g), _stream()),
-               "ppt_ball_query_f32")
+    if lengths is None:
+        _lib.check(_lib.lib().ppt_ball_query_f32(_p(xyz), _p(center), B, N, S, r2, K, _p(idx), _p(g), _stream()),
+                   "ppt_ball_query_f32")
+    else:
+        _chk_lengths(lengths, B)
+        _lib.check(_lib.lib().ppt_ball_query_ragged_f32(_p(xyz), _p(center), B, N, S, r2, K, _p(lengths), _p(idx), _p(g), _stream()),
+                   "ppt_ball_query_ragged_f32")
     if profiler is not None:
         profiler.end()
     return (idx, g) if want_grouped else idx

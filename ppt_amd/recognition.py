@@ -44,8 +44,9 @@ def _loaders(train_set, test_set, args, recipe, defaults):
     kw = dict(drop_last=False, seed=seed, rank=rank, world_size=world, use_height=bool(_arg(args, "use_height", defaults)))
     # main_cls.py:74-87; the test split is walked in its stored order, as run_fewshot walks it (the reference shuffles it too, which
     # moves no figure but the order of the per-class table)
-    return (DeviceBatchLoader(train_set, batch_size, npoints, recipe, train=True, shuffle=True, **kw),
-            DeviceBatchLoader(test_set, batch_size, npoints, recipe, train=False, shuffle=False, **kw))
+    # a set that carries lengths may hold clouds of differing length: the loader's one FPS launch then takes them (ragged=True)
+    return (DeviceBatchLoader(train_set, batch_size, npoints, recipe, train=True, shuffle=True, ragged=train_set.lengths is not None, **kw),
+            DeviceBatchLoader(test_set, batch_size, npoints, recipe, train=False, shuffle=False, ragged=test_set.lengths is not None, **kw))
 
 
 def _trainer(model, args, n_batches, defaults):

@@ -337,13 +337,16 @@ class Trainer:
             return None
         return model.text_stream()
 
-    def step(self, pc, label, check_finite=False):
-        """One iteration.  On a GPU the prompt side of the step (zero_grad, text tower, its backward, the
+    def step(self, pc, label, check_finite=False, lengths=None):
+        """One iteration (lengths: refused -- a ragged batch goes through model(pc, lengths=...) and a plain loss.backward(); the
+        step's graphs and ahead stages are keyed by the cloud's shape alone).  On a GPU the prompt side of the step (zero_grad, text tower, its backward, the
         gradient all-reduce, AdamW, the logit_scale clamp) is queued on the model's text stream, the point
         tower and the loss on the caller's stream.  With a fully frozen point side (head_type 0) nothing the
         point tower reads changes between iterations, so the caller's stream does not wait for the optimizer:
         iteration i+1's point tower overlaps iteration i's text backward.  `loss` and `pred` are ordinary
         tensors of the caller's stream; parameters are final after `finish()`."""
+        if lengths is not None:
+            raise ValueError("Trainer.step takes no lengths: run a ragged batch through model(pc, lengths=...) and loss.backward()")
         model = self.model
         if self.grad_calibration is None and not self._dry:      # (the first step of THIS trainer, whatever `it` a resume set)
             self.calibrate_gradients(pc, label)
