@@ -57,7 +57,9 @@ const char *ppt_strerror(int code);
  *    ppt_cloud_augment_f32 / ppt_cloud_draws_aug (csrc/cloud_augment.hip);
  *    ppt_train_meter_cls / ppt_train_meter_partseg (csrc/meters.hip); ppt_sgd_multi / ppt_adam_multi (csrc/optim.hip);
  *    ppt_fps_ragged_f32 / ppt_knn_group_ragged_f32 / ppt_ball_query_ragged_f32 / ppt_ball_query_multi_ragged_f32 (csrc/fps.hip,
- *    csrc/knn_group.hip: per-cloud row counts).
+ *    csrc/knn_group.hip: per-cloud row counts);
+ *    ppt_knn_group_packed_f32 / ppt_three_nn_interp_packed_fwd / ppt_scatter_rows_packed_bwd / ppt_pack_rows / ppt_unpack_rows /
+ *    ppt_partseg_metrics_ragged / ppt_train_meter_partseg_ragged (ragged clouds on packed rows: the part-seg decoder's tail).
  * 6: ppt_gemm_params.split16 / split_a_pow2 / split_b_pow2 (new trailing fields: fp32 operands as hi + lo half pairs),
  *    ppt_attention_fwd_split16 / ppt_attention_bwd_split16 (new), ppt_pointmlp_cloud_rstd / ppt_pointmlp_pq (new).
  * 5: ppt_labels_check (new), ppt_gemm256 (new: the 256-row macro-tile GEMM core), ppt_set_gemm256 / ppt_get_gemm256 (new),
@@ -141,6 +143,44 @@ int ppt_ball_query_ragged_f32(const float *xyz, const float *center, int B, int 
                               const int32_t *lengths, int64_t *idx, float *grouped_xyz, void *stream);
 int ppt_ball_query_multi_ragged_f32(const float *xyz, const float *center, int B, int Nmax, int S, const int32_t *lengths,
                                     const ppt_ball_multi *q, void *stream);
+
+/* ---- ragged clouds on PACKED ROWS: the per-point tail of the part-segmentation decoder -----------------------------------------
+ * Per-point tensors of a ragged batch are kept without their padding: R = sum(lengths) rows, cloud b owning rows
+ * offsets[b] .. offsets[b + 1] - 1 (offsets [B + 1] i32 on the device, the exclusive prefix sum of lengths [B] i32; the layout of
+ * the ragged text tower below).  Coordinates stay in their padded slab [B, Nmax, 3], Nmax the row stride; nothing behind row
+ * lengths[b] - 1 of a slab is read (the padding may hold NaN), packed outputs have exactly R rows and no row outside [0, R) is
+ * written.  Each kernel is the body of its uniform entry point, instantiated with a compile-time flag (the uniform entry points run
+ * the instantiation without it: the code they ran before).  The result for cloud b is bit-identical to the uniform entry point
+ * run on that cloud alone at N = lengths[b].  No floating-point atomics; every result is the same on every run.
+ * Offsets and lengths are device memory the entry points cannot look into.  The kernels CLAMP them -- an offset into [0, R], a
+ * cloud's row count into [0, Nmax] ([1, Nmax] where labels[b, 0] is read) -- so that no access leaves the slabs or the R packed
+ * rows: that is memory safety, not a semantic; a table that is not the prefix sum of lengths <= Nmax is the caller's error.
+ *   knn_group_packed       ppt_knn_group_f32 with ragged QUERIES: xyz [B,S,3] sources (uniform, or ragged through lengths [B] as
+ *                          for ppt_knn_group_ragged_f32; lengths == NULL: uniform), center [B,Gmax,3] queries of which cloud b has
+ *                          q_lengths[b], -> nbr_idx [R,k] i64 / neighborhood [R,k,3] / nbr_dist [R,k] (each may be NULL) in packed
+ *                          rows, R = sum(q_lengths), q_offsets its prefix sum.  Same expanded-form distances, (distance, index) tie
+ *                          rule and degenerate-tie path.  A workgroup whose query tile lies behind its cloud's end leaves before
+ *                          it loads a coordinate.  Limits as ppt_knn_group_f32 (k <= 64, k <= S <= 8192).
+ *   three_nn_interp_packed ppt_three_nn_interp_fwd on packed targets: idx / dist [R,3] (knn_group_packed, k = 3), points2 [B,S,D2],
+ *                          out [R, ld_out] in out_dtype, weight_out [R,3] (may be NULL).  points1 is never packed: its columns are
+ *                          [cloud_cols[b, :Dc] | points1[b, n, :Dp]], cloud_cols [B,Dc] one row per CLOUD (the one-hot class
+ *                          label) and points1 [B,Nmax,Dp] a padded slab (the coordinates); either may be absent (width 0, NULL).
+ *   scatter_rows_packed    ppt_scatter_rows_bwd with cloud b's entry list the rows_div * (offsets[b+1] - offsets[b]) entries from
+ *                          rows_div * offsets[b] on: idx / weight [R * rows_div], d_rows [R, ld] -> d_src [B,S,C].  Owner-computes,
+ *                          ascending entry order; a cloud's list may have any length (the LDS staging takes it in chunks).
+ *   pack_rows / unpack_rows  padded [B,Nmax,row_bytes] <-> packed [R,row_bytes], rows moved as bytes (any dtype, any width; 16-,
+ *                          8-, 4-, 2- or 1-byte accesses by what row_bytes and the two addresses allow).  unpack writes every
+ *                          row of every slab, ZERO behind the cloud's end; pack reads nothing there.  Each is the other's backward. */
+int ppt_knn_group_packed_f32(const float *xyz, const float *center, int B, int S, int Gmax, int k, const int32_t *lengths,
+                             const int32_t *q_lengths, const int32_t *q_offsets, int R, int64_t *nbr_idx, float *neighborhood,
+                             float *nbr_dist, void *stream);
+int ppt_three_nn_interp_packed_fwd(const float *cloud_cols, int Dc, const float *points1, int Dp, const float *points2, int D2,
+                                   const int64_t *idx, const float *dist, const int32_t *offsets, int B, int Nmax, int R, int S,
+                                   void *out, int out_dtype, int ld_out, float *weight_out, void *stream);
+int ppt_scatter_rows_packed_bwd(const int64_t *idx, const float *weight, const float *d_rows, int64_t ld, int col_off,
+                                const int32_t *offsets, int B, int R, int rows_div, int S, int C, float *d_src, void *stream);
+int ppt_pack_rows(const void *padded, void *packed, const int32_t *offsets, int B, int Nmax, int R, int64_t row_bytes, void *stream);
+int ppt_unpack_rows(const void *packed, void *padded, const int32_t *offsets, int B, int Nmax, int R, int64_t row_bytes, void *stream);
 
 /* ---- GEMM with fused prologue / epilogue ----------------------------------------------------
  * C[M,N] = epilogue( prologue(A)[M,K] . B[N,K]^T ).  A and B are K-contiguous (torch Linear /
@@ -920,6 +960,17 @@ int ppt_partseg_metrics_chunks(int N);
 int ppt_partseg_metrics(const float *logits, const int64_t *labels, float smoothing, int B, int N, int P,
                         const int32_t *part_start, const int32_t *part_count, int max_parts, int32_t *records, float *partial,
                         void *stream);
+/* partseg_metrics_ragged: the same kernel body (a compile-time flag) over padded logits [B, Nmax, P] and labels [B, Nmax] with
+ *   lengths [B] i32 on the device: counts, loss sum and the per-part terms run over rows < lengths[b] only, and no label or logit
+ *   behind them enters anything (the padding may hold NaN and any label).  The category still comes from labels[b, 0].  The record
+ *   of cloud b is, byte for byte, the record ppt_partseg_metrics writes for that cloud alone at N = lengths[b] ([5] included: the
+ *   chunks its own rows fill); the host divides the loss sums by R = sum(lengths), which is also the accuracy's denominator.
+ *   partial: B * ppt_partseg_metrics_chunks(Nmax) floats -- the chunks are cut for Nmax; one wholly behind a cloud's end counts
+ *   nothing and still takes part in the last-to-arrive fold.  A length outside 1 .. Nmax is the caller's error and is clamped into
+ *   that range (memory safety only).  PPT_EINVAL for lengths == NULL and for everything ppt_partseg_metrics refuses. */
+int ppt_partseg_metrics_ragged(const float *logits, const int64_t *labels, const int32_t *lengths, float smoothing, int B, int Nmax,
+                               int P, const int32_t *part_start, const int32_t *part_count, int max_parts, int32_t *records,
+                               float *partial, void *stream);
 
 /* ---- training meters (ABI 7, additive; csrc/meters.hip; host side: ppt_amd/recognition.py, ppt_amd/partseg.py) ----------------
  * What train() of main_cls.py:200-217 / main_partseg.py:218-243 takes out of a step with .item() reads, as ONE launch per step on
@@ -951,6 +1002,13 @@ int ppt_train_meter_cls(const float *logits, const int64_t *labels, const float 
 int ppt_train_meter_partseg(const float *logits, const int64_t *labels, const float *loss, int B, int N, int P,
                             const int32_t *part_start, const int32_t *part_count, double weight, int metered, double *rec,
                             uint32_t *scratch, void *stream);
+/* train_meter_partseg_ragged: the same kernel body (a compile-time flag) over padded logits [B, Nmax, P] / labels [B, Nmax] with
+ *   lengths [B] i32 on the device: correct counts rows < lengths[b] only and acc = (float)correct / (float)sum(lengths); nothing
+ *   behind a cloud's end is read.  Chunks are cut for Nmax; one wholly behind a cloud's end counts nothing, still draws its ticket,
+ *   and the scratch ends all zero.  Lengths are clamped into 1 .. Nmax (memory safety only).  PPT_EINVAL for lengths == NULL. */
+int ppt_train_meter_partseg_ragged(const float *logits, const int64_t *labels, const int32_t *lengths, const float *loss, int B,
+                                   int Nmax, int P, const int32_t *part_start, const int32_t *part_count, double weight, int metered,
+                                   double *rec, uint32_t *scratch, void *stream);
 
 /* ---- few-shot linear probe (ABI 7, additive; csrc/logreg.hip; host side: ppt_amd/probe.py) ------------------------------------
  * What the reference's linear_probe.py:55,68,73 asks of sklearn.LogisticRegression(solver="lbfgs", penalty="l2", C=c).fit and

@@ -133,6 +133,15 @@ _SIGNATURES = {
     "ppt_knn_group_ragged_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ppt_ball_query_multi_ragged_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, ctypes.POINTER(BallMulti), c_void_p]),
     "ppt_ball_query_ragged_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # ragged clouds on packed rows (R = sum(lengths) rows, offsets [B+1] i32 on the device)
+    "ppt_knn_group_packed_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p]),
+    "ppt_three_nn_interp_packed_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                               c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ppt_scatter_rows_packed_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                            c_void_p, c_void_p]),
+    "ppt_pack_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
+    "ppt_unpack_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
     "ppt_gather_add": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                c_void_p, c_void_p, c_void_p]),
     "ppt_pool_finish": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64,
@@ -264,6 +273,10 @@ _SIGNATURES = {
     "ppt_partseg_metrics_chunks": (c_int, [c_int]),
     "ppt_partseg_metrics": (c_int, [c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                     c_void_p]),
+    "ppt_partseg_metrics_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                           c_void_p, c_void_p, c_void_p]),
+    "ppt_train_meter_partseg_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                               ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p]),
     "ppt_train_meter_cls": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p]),
     "ppt_train_meter_partseg": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_double, c_int,
                                         c_void_p, c_void_p, c_void_p]),

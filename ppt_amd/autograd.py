@@ -244,11 +244,69 @@ class _FeaturePropagation(torch.autograd.Function):
         return dp2, dW0, db0, dg0, dbe0, dW1, db1, dg1, dbe1, None, None, None, None, None
 
 
-def feature_propagation(mod, points1, points2, idx, dist, prec):
-    """mod: a PointNetFeaturePropagation with two conv + bn layers; idx / dist [B,N,3] from the 3-NN search."""
+class _FeaturePropagationPacked(torch.autograd.Function):
+    """_FeaturePropagation for the targets of a ragged batch, on PACKED rows (R = sum(lengths), cloud b owning rows offsets[b] ..
+    offsets[b+1]-1): idx / dist [R,3], the points1 columns [cloud_cols[b] | points1[b, n]] taken from a per-cloud row and the
+    PADDED slab as they are (ppt_three_nn_interp_packed_fwd), the two conv + BatchNorm + ReLU layers -- the same GEMM and
+    BatchNorm nodes, on R rows: the statistics are over the rows that exist by construction -- and the backward with the packed
+    owner-computes scatter (ppt_scatter_rows_packed_bwd).  -> [R, mlp[-1]] f32."""
+
+    @staticmethod
+    def forward(ctx, points2, w0, b0, g0, be0, w1, b1, g1, be1, mod, idx, dist, points1, prec, cloud_cols, offsets):
+        training = mod.training
+        R = idx.shape[0]
+        p2 = points2.detach().float().contiguous()
+        p1 = points1.detach().float().contiguous() if points1 is not None else None
+        cc = cloud_cols.detach().float().contiguous() if cloud_cols is not None else None
+        rows, wgt = ops.three_nn_interp_packed(cc, p1, p2, idx, dist, offsets, prec, _mult(prec))
+        h0, s0 = _conv_bn_relu_fwd(rows, w0, b0, mod.mlp_bns[0], training, prec, prec)
+        h1, s1 = _conv_bn_relu_fwd(h0, w1, b1, mod.mlp_bns[1], training, prec, torch.float32)
+        ctx.s0, ctx.s1, ctx.idx, ctx.wgt, ctx.offsets = s0, s1, idx, wgt, offsets
+        ctx.training, ctx.prec, ctx.w0, ctx.w1 = training, prec, w0, w1
+        ctx.D1 = (0 if p1 is None else p1.shape[2]) + (0 if cc is None else cc.shape[1])
+        ctx.S, ctx.D2 = p2.shape[1], p2.shape[2]
+        ctx.grad_scale = gradscale.current(prec, default_rows=R)               # a 16-bit backward stage (ppt_amd/gradscale.py)
+        return h1
+
+    @staticmethod
+    @gradscale.scaled_backward
+    def backward(ctx, dout):
+        dh0, dW1, db1, dg1, dbe1 = _conv_bn_relu_bwd(dout, ctx.s1, ctx.training, ctx.prec, ctx.w1, True)
+        d_rows, dW0, db0, dg0, dbe0 = _conv_bn_relu_bwd(dh0, ctx.s0, ctx.training, ctx.prec, ctx.w0, ctx.needs_input_grad[0])
+        dp2 = None
+        if ctx.needs_input_grad[0]:
+            dp2 = ops.scatter_rows_packed_bwd(ctx.idx.view(-1), ctx.wgt.view(-1), d_rows, ctx.D1, 3, ctx.offsets, ctx.S, ctx.D2)
+        return dp2, dW0, db0, dg0, dbe0, dW1, db1, dg1, dbe1, None, None, None, None, None, None, None
+
+
+def feature_propagation(mod, points1, points2, idx, dist, prec, packed=None):
+    """mod: a PointNetFeaturePropagation with two conv + bn layers; idx / dist [B,N,3] from the 3-NN search.
+    packed = (cloud_cols [B,Dc] | None, offsets [B+1] i32): the targets are the packed rows of a ragged batch -- idx / dist [R,3],
+    points1 [B,Nmax,Dp] | None the PADDED slab -- and the result is [R, mlp[-1]] (_FeaturePropagationPacked)."""
     c0, c1, n0, n1 = mod.mlp_convs[0], mod.mlp_convs[1], mod.mlp_bns[0], mod.mlp_bns[1]
+    if packed is not None:
+        return _FeaturePropagationPacked.apply(points2, c0.weight, c0.bias, n0.weight, n0.bias, c1.weight, c1.bias, n1.weight, n1.bias,
+                                               mod, idx, dist, points1, prec, packed[0], packed[1])
     return _FeaturePropagation.apply(points2, c0.weight, c0.bias, n0.weight, n0.bias, c1.weight, c1.bias, n1.weight, n1.bias,
                                      mod, idx, dist, points1, prec)
+
+
+class _UnpackRows(torch.autograd.Function):
+    """packed [R, ...] -> padded [B, Nmax, ...], zero rows behind every cloud's end (ppt_unpack_rows); the backward packs the
+    gradient: what arrives for a padding row goes nowhere."""
+
+    @staticmethod
+    def forward(ctx, packed, offsets, Nmax):
+        ctx.offsets, ctx.R = offsets, packed.shape[0]
+        return ops.unpack_rows(packed.detach().contiguous(), offsets, Nmax)
+
+    @staticmethod
+    def backward(ctx, dpadded):
+        return ops.pack_rows(dpadded.contiguous(), ctx.offsets, ctx.R), None, None
+
+
+def unpack_rows(packed, offsets, Nmax):
+    return _UnpackRows.apply(packed, offsets, Nmax)
 
 
 class _ConvBNReLURows(torch.autograd.Function):

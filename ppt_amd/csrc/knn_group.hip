@@ -63,13 +63,26 @@ __device__ __forceinline__ void stage_cloud(const float *__restrict__ p, int N, 
     }
 }
 
-template <int W, bool RAGGED>
+// QRAG (ppt_knn_group_packed_f32): the QUERIES are ragged too -- cloud b has q_lengths[b] of them, rows 0 .. q_lengths[b]-1 of its
+// [G, 3] slab (G the row stride), and query c of cloud b writes PACKED output row q_offsets[b] + c (q_offsets the exclusive prefix
+// sum of q_lengths).  A workgroup whose query tile starts behind its cloud's end leaves before it loads anything else.  Like
+// RAGGED a compile-time flag with its pointers behind every other argument: the other instantiations never look at them.
+template <int W, bool RAGGED, bool QRAG>
 __global__ __launch_bounds__(W * 64) void knn_group_kernel(const float *__restrict__ xyz,
                                                            const float *__restrict__ center, int N, int G,
                                                            int k, int cpb, int64_t *__restrict__ nbr_idx,
                                                            float *__restrict__ nbhd, float *__restrict__ ndist,
-                                                           const int32_t *__restrict__ lengths)
+                                                           const int32_t *__restrict__ lengths,
+                                                           const int32_t *__restrict__ q_lengths,
+                                                           const int32_t *__restrict__ q_offsets, int R)
 {
+    int g = G, q_off = 0;
+    if constexpr (QRAG) {
+        g = max(0, min((int)q_lengths[blockIdx.y], G));              // (clamped: a bad length must not leave the slab ...
+        if ((int)blockIdx.x * cpb >= g) return;
+        q_off = max(0, min((int)q_offsets[blockIdx.y], R));          // ... a bad offset not the packed outputs)
+        g = min(g, R - q_off);
+    }
     extern __shared__ __align__(16) unsigned char smem[];
     float4 *cloud = reinterpret_cast<float4 *>(smem);                                   // [N]
     unsigned long long *lists = reinterpret_cast<unsigned long long *>(smem + (size_t)N * 16);  // [W][KNN_CAP]
@@ -82,7 +95,7 @@ __global__ __launch_bounds__(W * 64) void knn_group_kernel(const float *__restri
     __syncthreads();
 
     unsigned long long *list = lists + (size_t)w * KNN_CAP;
-    const int c_end = min(G, (int)(blockIdx.x + 1) * cpb);
+    const int c_end = min(g, (int)(blockIdx.x + 1) * cpb);
     for (int c = blockIdx.x * cpb + w; c < c_end; c += W) {
         const float *q = center + ((size_t)b * G + c) * 3;
         const float qx = q[0], qy = q[1], qz = q[2];
@@ -117,9 +130,10 @@ __global__ __launch_bounds__(W * 64) void knn_group_kernel(const float *__restri
         }
         wave_lds_fence();
 
-        int64_t *oi = nbr_idx ? nbr_idx + ((size_t)b * G + c) * k : nullptr;
-        float *on = nbhd ? nbhd + ((size_t)b * G + c) * k * 3 : nullptr;
-        float *od = ndist ? ndist + ((size_t)b * G + c) * k : nullptr;
+        const size_t orow = QRAG ? (size_t)q_off + c : (size_t)b * G + c;
+        int64_t *oi = nbr_idx ? nbr_idx + orow * k : nullptr;
+        float *on = nbhd ? nbhd + orow * k * 3 : nullptr;
+        float *od = ndist ? ndist + orow * k : nullptr;
         if (cnt <= KNN_CAP) {
             // rank by counting (keys are unique: the index is part of the key)
             for (int e0 = 0; e0 < cnt; e0 += 64) {
@@ -402,9 +416,10 @@ extern "C" int ppt_ball_query_multi_ragged_f32(const float *xyz, const float *ce
     return ball_query_multi_launch<true>(xyz, center, lengths, B, Nmax, S, q, stream);
 }
 
-template <bool RAGGED>
+template <bool RAGGED, bool QRAG = false>
 static int knn_group_launch(const float *xyz, const float *center, const int32_t *lengths, int B, int N, int G, int k,
-                            int64_t *nbr_idx, float *neighborhood, float *nbr_dist, void *stream)
+                            int64_t *nbr_idx, float *neighborhood, float *nbr_dist, void *stream,
+                            const int32_t *q_lengths = nullptr, const int32_t *q_offsets = nullptr, int R = 0)
 {
     if (!xyz || !center || B <= 0 || N <= 0 || G <= 0 || k <= 0 || k > 64 || k > N || N > 8192)
         return PPT_EINVAL;
@@ -412,13 +427,13 @@ static int knn_group_launch(const float *xyz, const float *center, const int32_t
     const size_t lds = (size_t)N * 16 + (size_t)W * KNN_CAP * 8;
     // the opt-in to > 64 KB of dynamic LDS is made ONCE per kernel (thread-safe static initialisation), for the
     // largest cloud the entry point accepts -- not on every launch
-    static const hipError_t optin = hipFuncSetAttribute((const void *)knn_group_kernel<W, RAGGED>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    static const hipError_t optin = hipFuncSetAttribute((const void *)knn_group_kernel<W, RAGGED, QRAG>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                          8192 * 16 + W * KNN_CAP * 8);
     if (lds > 64 * 1024 && optin != hipSuccess) return PPT_ELAUNCH;
     const int cpb = 32;
     dim3 grid((G + cpb - 1) / cpb, B);
-    hipLaunchKernelGGL((knn_group_kernel<W, RAGGED>), grid, dim3(W * 64), lds, ppt_stream(stream), xyz, center, N, G, k,
-                       cpb, nbr_idx, neighborhood, nbr_dist, lengths);
+    hipLaunchKernelGGL((knn_group_kernel<W, RAGGED, QRAG>), grid, dim3(W * 64), lds, ppt_stream(stream), xyz, center, N, G, k,
+                       cpb, nbr_idx, neighborhood, nbr_dist, lengths, q_lengths, q_offsets, R);
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }
@@ -434,6 +449,18 @@ extern "C" int ppt_knn_group_ragged_f32(const float *xyz, const float *center, i
 {
     if (!lengths) return PPT_EINVAL;
     return knn_group_launch<true>(xyz, center, lengths, B, Nmax, G, k, nbr_idx, neighborhood, nbr_dist, stream);
+}
+
+extern "C" int ppt_knn_group_packed_f32(const float *xyz, const float *center, int B, int S, int Gmax, int k, const int32_t *lengths,
+                                        const int32_t *q_lengths, const int32_t *q_offsets, int R, int64_t *nbr_idx,
+                                        float *neighborhood, float *nbr_dist, void *stream)
+{
+    if (!q_lengths || !q_offsets || R <= 0) return PPT_EINVAL;
+    if (lengths)
+        return knn_group_launch<true, true>(xyz, center, lengths, B, S, Gmax, k, nbr_idx, neighborhood, nbr_dist, stream, q_lengths,
+                                            q_offsets, R);
+    return knn_group_launch<false, true>(xyz, center, nullptr, B, S, Gmax, k, nbr_idx, neighborhood, nbr_dist, stream, q_lengths,
+                                         q_offsets, R);
 }
 
 template <bool RAGGED>

@@ -81,11 +81,16 @@ __global__ __launch_bounds__(MT_THREADS) void train_meter_cls_kernel(const float
     }
 }
 
+// RAGGED (ppt_train_meter_partseg_ragged): N is the slabs' row stride, cloud b its first lengths[b] rows; nothing behind them is
+// read, a chunk wholly behind a cloud's end counts nothing and still draws its ticket, and the accuracy's denominator is the sum of
+// the lengths.  A compile-time flag, lengths the last argument: the uniform instantiation is the kernel it was.
+template <bool RAGGED>
 __global__ __launch_bounds__(MT_THREADS) void train_meter_partseg_kernel(const float *__restrict__ logits, const int64_t *__restrict__ labels,
                                                                          const float *__restrict__ loss, int B, int N, int P, int chunks,
                                                                          const int32_t *__restrict__ part_start,
                                                                          const int32_t *__restrict__ part_count, double weight,
-                                                                         int metered, double *__restrict__ rec, unsigned *scratch)
+                                                                         int metered, double *__restrict__ rec, unsigned *scratch,
+                                                                         const int32_t *__restrict__ lengths)
 {
     __shared__ int wave_correct[MT_WAVES], wave_bad[MT_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -102,8 +107,10 @@ __global__ __launch_bounds__(MT_THREADS) void train_meter_partseg_kernel(const f
     start = max(0, min(start, P));
     count = max(0, min(count, P - start));
 
+    int n_rows = N;
+    if constexpr (RAGGED) n_rows = max(1, min((int)lengths[b], N));      // (clamped: a bad length must not leave the slab)
     bool hit = false, out = false;
-    if (n < N) {
+    if (n < n_rows) {
         const int64_t t = lab[n];
         out = t < 0 || t >= (int64_t)P;
         if (count > 0) {
@@ -137,7 +144,12 @@ __global__ __launch_bounds__(MT_THREADS) void train_meter_partseg_kernel(const f
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned total = __hip_atomic_load(scratch + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned flags = __hip_atomic_load(scratch + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    mt_fold(rec, loss, mt_ratio((long long)total, (long long)B * N), weight, metered, flags != 0);
+    long long points = (long long)B * N;
+    if constexpr (RAGGED) {
+        points = 0;
+        for (int i = 0; i < B; i++) points += max(1, min((int)lengths[i], N));
+    }
+    mt_fold(rec, loss, mt_ratio((long long)total, points), weight, metered, flags != 0);
     __hip_atomic_store(scratch + 0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(scratch + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(scratch + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -156,9 +168,9 @@ extern "C" int ppt_train_meter_cls(const float *logits, const int64_t *labels, c
     return PPT_OK;
 }
 
-extern "C" int ppt_train_meter_partseg(const float *logits, const int64_t *labels, const float *loss, int B, int N, int P,
-                                       const int32_t *part_start, const int32_t *part_count, double weight, int metered, double *rec,
-                                       uint32_t *scratch, void *stream)
+static int train_meter_partseg_launch(const float *logits, const int64_t *labels, const int32_t *lengths, const float *loss, int B, int N,
+                                      int P, const int32_t *part_start, const int32_t *part_count, double weight, int metered,
+                                      double *rec, uint32_t *scratch, void *stream)
 {
     if (!logits || !labels || !loss || !part_start || !part_count || !rec || !scratch || B <= 0 || N <= 0 || P <= 0) return PPT_EINVAL;
     if (((uintptr_t)rec & 7) || ((uintptr_t)logits & 3) || ((uintptr_t)loss & 3) || ((uintptr_t)labels & 7) || ((uintptr_t)scratch & 3))
@@ -166,8 +178,28 @@ extern "C" int ppt_train_meter_partseg(const float *logits, const int64_t *label
     if (P > 64) return PPT_EUNSUPPORTED;
     const int chunks = (N + MT_CHUNK - 1) / MT_CHUNK;
     if ((int64_t)B * chunks > 0x7fffffffLL || (int64_t)B * N > 0x7fffffffLL) return PPT_EINVAL;
-    hipLaunchKernelGGL(train_meter_partseg_kernel, dim3((unsigned)(B * chunks)), dim3(MT_THREADS), 0, ppt_stream(stream), logits, labels,
-                       loss, B, N, P, chunks, part_start, part_count, weight, metered ? 1 : 0, rec, (unsigned *)scratch);
+    if (lengths)
+        hipLaunchKernelGGL(train_meter_partseg_kernel<true>, dim3((unsigned)(B * chunks)), dim3(MT_THREADS), 0, ppt_stream(stream), logits,
+                           labels, loss, B, N, P, chunks, part_start, part_count, weight, metered ? 1 : 0, rec, (unsigned *)scratch, lengths);
+    else
+        hipLaunchKernelGGL(train_meter_partseg_kernel<false>, dim3((unsigned)(B * chunks)), dim3(MT_THREADS), 0, ppt_stream(stream), logits,
+                           labels, loss, B, N, P, chunks, part_start, part_count, weight, metered ? 1 : 0, rec, (unsigned *)scratch, lengths);
     PPT_CHECK_LAUNCH();
     return PPT_OK;
+}
+
+extern "C" int ppt_train_meter_partseg(const float *logits, const int64_t *labels, const float *loss, int B, int N, int P,
+                                       const int32_t *part_start, const int32_t *part_count, double weight, int metered, double *rec,
+                                       uint32_t *scratch, void *stream)
+{
+    return train_meter_partseg_launch(logits, labels, nullptr, loss, B, N, P, part_start, part_count, weight, metered, rec, scratch, stream);
+}
+
+extern "C" int ppt_train_meter_partseg_ragged(const float *logits, const int64_t *labels, const int32_t *lengths, const float *loss, int B,
+                                              int Nmax, int P, const int32_t *part_start, const int32_t *part_count, double weight,
+                                              int metered, double *rec, uint32_t *scratch, void *stream)
+{
+    if (!lengths) return PPT_EINVAL;
+    return train_meter_partseg_launch(logits, labels, lengths, loss, B, Nmax, P, part_start, part_count, weight, metered, rec, scratch,
+                                      stream);
 }

@@ -77,18 +77,26 @@ __global__ __launch_bounds__(256) void cls_metrics_kernel(const float *__restric
     }
 }
 
+// RAGGED (ppt_partseg_metrics_ragged): N is the row stride of the slabs and cloud b its first lengths[b] rows; the chunks are cut
+// for N, a chunk wholly behind the cloud's end counts nothing (its loss partial is 0) but still draws its ticket.  Everything the
+// kernel takes from a row -- label, logits -- it takes from rows < lengths[b] only (the 16-byte staging loads may touch up to three
+// floats of the next row inside the same allocation; they are dropped unlooked-at, as at a cloud boundary of the uniform form).
+// A compile-time flag, lengths the last argument: the uniform instantiation is the kernel it was.
+template <bool RAGGED>
 __global__ __launch_bounds__(PS_TILE) void partseg_metrics_kernel(const float *__restrict__ logits, const int64_t *__restrict__ labels,
                                                                   float smoothing, int N, int P, size_t total, int chunks,
                                                                   const int32_t *__restrict__ part_start,
                                                                   const int32_t *__restrict__ part_count, int32_t *records,
-                                                                  float *partial)
+                                                                  float *partial, const int32_t *__restrict__ lengths)
 {
     __shared__ float tile[PS_TILE * (64 + 1) + 4];
     __shared__ int wave_counts[PS_WAVES][PS_SLOTS];
     __shared__ double wave_loss[PS_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x / chunks, chunk = blockIdx.x - b * chunks;
-    const int n0 = chunk * PS_CHUNK, n1 = min(N, n0 + PS_CHUNK);
+    int n_rows = N;
+    if constexpr (RAGGED) n_rows = max(1, min((int)lengths[b], N));      // (clamped: a bad length must not leave the slab)
+    const int n0 = chunk * PS_CHUNK, n1 = min(n_rows, n0 + PS_CHUNK);
     const int64_t *lab = labels + (size_t)b * N;
     int32_t *rec = records + (size_t)b * PPT_PARTSEG_REC;
 
@@ -224,6 +232,8 @@ __global__ __launch_bounds__(PS_TILE) void partseg_metrics_kernel(const float *_
             for (int c = 0; c < chunks; c++)
                 s += (double)__hip_atomic_load(partial + (size_t)b * chunks + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             rec[4] = (int)__float_as_uint((float)s);
+            // the record of the cloud alone: the chunks ITS rows fill (the counter above has counted the launch's)
+            if constexpr (RAGGED) rec[5] = (n_rows + PS_CHUNK - 1) / PS_CHUNK;
         }
     }
 }
@@ -239,9 +249,9 @@ extern "C" int ppt_cls_metrics(const float *logits, const int64_t *labels, float
 
 extern "C" int ppt_partseg_metrics_chunks(int N) { return N <= 0 ? 0 : (N + PS_CHUNK - 1) / PS_CHUNK; }
 
-extern "C" int ppt_partseg_metrics(const float *logits, const int64_t *labels, float smoothing, int B, int N, int P,
-                                   const int32_t *part_start, const int32_t *part_count, int max_parts, int32_t *records,
-                                   float *partial, void *stream)
+static int partseg_metrics_launch(const float *logits, const int64_t *labels, const int32_t *lengths, float smoothing, int B, int N,
+                                  int P, const int32_t *part_start, const int32_t *part_count, int max_parts, int32_t *records,
+                                  float *partial, void *stream)
 {
     if (!logits || !labels || !part_start || !part_count || !records || !partial || B <= 0 || N <= 0 || P <= 0 || max_parts <= 0)
         return PPT_EINVAL;
@@ -251,8 +261,28 @@ extern "C" int ppt_partseg_metrics(const float *logits, const int64_t *labels, f
     if ((int64_t)B * chunks > 0x7fffffffLL) return PPT_EINVAL;
     // the chunks of a cloud ADD into its record, and its arrival counter starts at zero
     if (hipMemsetAsync(records, 0, sizeof(int32_t) * PPT_PARTSEG_REC * (size_t)B, ppt_stream(stream)) != hipSuccess) return PPT_ELAUNCH;
-    hipLaunchKernelGGL(partseg_metrics_kernel, dim3((unsigned)(B * chunks)), dim3(PS_TILE), 0, ppt_stream(stream), logits, labels,
-                       smoothing, N, P, (size_t)B * N * P, chunks, part_start, part_count, records, partial);
+    if (lengths)
+        hipLaunchKernelGGL(partseg_metrics_kernel<true>, dim3((unsigned)(B * chunks)), dim3(PS_TILE), 0, ppt_stream(stream), logits,
+                           labels, smoothing, N, P, (size_t)B * N * P, chunks, part_start, part_count, records, partial, lengths);
+    else
+        hipLaunchKernelGGL(partseg_metrics_kernel<false>, dim3((unsigned)(B * chunks)), dim3(PS_TILE), 0, ppt_stream(stream), logits,
+                           labels, smoothing, N, P, (size_t)B * N * P, chunks, part_start, part_count, records, partial, lengths);
     PPT_CHECK_LAUNCH();
     return PPT_OK;
+}
+
+extern "C" int ppt_partseg_metrics(const float *logits, const int64_t *labels, float smoothing, int B, int N, int P,
+                                   const int32_t *part_start, const int32_t *part_count, int max_parts, int32_t *records,
+                                   float *partial, void *stream)
+{
+    return partseg_metrics_launch(logits, labels, nullptr, smoothing, B, N, P, part_start, part_count, max_parts, records, partial, stream);
+}
+
+extern "C" int ppt_partseg_metrics_ragged(const float *logits, const int64_t *labels, const int32_t *lengths, float smoothing, int B,
+                                          int Nmax, int P, const int32_t *part_start, const int32_t *part_count, int max_parts,
+                                          int32_t *records, float *partial, void *stream)
+{
+    if (!lengths) return PPT_EINVAL;
+    return partseg_metrics_launch(logits, labels, lengths, smoothing, B, Nmax, P, part_start, part_count, max_parts, records, partial,
+                                  stream);
 }

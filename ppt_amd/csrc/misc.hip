@@ -470,3 +470,76 @@ extern "C" int ppt_reduce_rows(const float *partial, int P, int D, float *out, i
     PPT_CHECK_LAUNCH();
     return PPT_OK;
 }
+
+// ---- packed rows <-> padded slabs (ragged clouds: cloud b owns the packed rows offsets[b] .. offsets[b + 1] - 1 and the first
+// offsets[b + 1] - offsets[b] rows of its slab of Nmax rows) -------------------------------------------------------------------------
+// Rows are moved as bytes, VB of them per thread: 16 where the row size and both addresses allow, else 8 / 4 / 2 / 1 (P = 50 fp32
+// logits: 200-byte rows, 8-byte moves).  grid.y = cloud.  UNPACK writes every row of the slab, zero behind the cloud's end; pack
+// reads nothing behind it and writes the cloud's packed rows only.
+namespace {
+
+template <int VB> struct bytes_t;
+template <> struct bytes_t<16> { using type = uint4; };
+template <> struct bytes_t<8> { using type = uint2; };
+template <> struct bytes_t<4> { using type = uint32_t; };
+template <> struct bytes_t<2> { using type = uint16_t; };
+template <> struct bytes_t<1> { using type = uint8_t; };
+
+template <int VB, bool UNPACK>
+__global__ __launch_bounds__(256) void pack_rows_kernel(const void *__restrict__ src, void *__restrict__ dst,
+                                                        const int32_t *__restrict__ offsets, int Nmax, int R, int row_vecs)
+{
+    using V = typename bytes_t<VB>::type;
+    const int b = blockIdx.y;
+    // (clamped: a bad offset table must leave neither the R packed rows nor the slab)
+    const int r0 = max(0, min((int)offsets[b], R));
+    const int len = max(0, min(min((int)offsets[b + 1], R) - r0, Nmax));
+    const int64_t total = (int64_t)(UNPACK ? Nmax : len) * row_vecs;
+    const V *s = static_cast<const V *>(src);
+    V *d = static_cast<V *>(dst);
+    const int64_t slab = (int64_t)b * Nmax * row_vecs, packed = (int64_t)r0 * row_vecs;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        if constexpr (UNPACK) {
+            V v{};
+            if (i < (int64_t)len * row_vecs) v = s[packed + i];
+            d[slab + i] = v;
+        } else {
+            d[packed + i] = s[slab + i];
+        }
+    }
+}
+
+template <bool UNPACK>
+int pack_rows_launch(const void *src, void *dst, const int32_t *offsets, int B, int Nmax, int R, int64_t row_bytes, void *stream)
+{
+    if (!src || !dst || !offsets || B <= 0 || Nmax <= 0 || R <= 0 || row_bytes <= 0 || row_bytes > 0x7fffffffLL) return PPT_EINVAL;
+    const uintptr_t a = (uintptr_t)src | (uintptr_t)dst | (uintptr_t)row_bytes;
+    const int vb = !(a & 15) ? 16 : !(a & 7) ? 8 : !(a & 3) ? 4 : !(a & 1) ? 2 : 1;
+    const int row_vecs = (int)(row_bytes / vb);
+    const int64_t total = (int64_t)Nmax * row_vecs;
+    const dim3 grid((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096), B);
+#define PPT_PK(VB)                                                                                                             \
+    hipLaunchKernelGGL((pack_rows_kernel<VB, UNPACK>), grid, dim3(256), 0, ppt_stream(stream), src, dst, offsets, Nmax, R, row_vecs)
+    if (vb == 16) PPT_PK(16);
+    else if (vb == 8) PPT_PK(8);
+    else if (vb == 4) PPT_PK(4);
+    else if (vb == 2) PPT_PK(2);
+    else PPT_PK(1);
+#undef PPT_PK
+    PPT_CHECK_LAUNCH();
+    return PPT_OK;
+}
+
+}  // namespace
+
+extern "C" int ppt_pack_rows(const void *padded, void *packed, const int32_t *offsets, int B, int Nmax, int R, int64_t row_bytes,
+                             void *stream)
+{
+    return pack_rows_launch<false>(padded, packed, offsets, B, Nmax, R, row_bytes, stream);
+}
+
+extern "C" int ppt_unpack_rows(const void *packed, void *padded, const int32_t *offsets, int B, int Nmax, int R, int64_t row_bytes,
+                               void *stream)
+{
+    return pack_rows_launch<true>(packed, padded, offsets, B, Nmax, R, row_bytes, stream);
+}

@@ -242,7 +242,15 @@ class DeviceBatchLoader:
     Batch i + `ahead` is queued on graphs.shared_group_stream() before batch i is yielded.  Every yielded tensor is a fresh allocation
     made under that stream, record_stream-ed on the consumer's stream, and carries its completion event as `_ppt_ready`
     (graphs.wait_inputs: the model's input-only stages start behind it on their own stream).  The iteration never synchronises.
-    No stream is created here: see DevicePrefetcher._stream for what a further stream does to the two-stream schedule."""
+    No stream is created here: see DevicePrefetcher._stream for what a further stream does to the two-stream schedule.
+
+    recipe "shapenetpart" with ragged=True is the WHOLE-SHAPE mode: no `sel` draw (np.random.choice(len, npoints, replace=True) labels
+    a resample with duplicates, not the shape), every stored row of every cloud.  It yields (pc [B, Nmax_set, 3], cls [B, 1] i32,
+    seg [B, Nmax_set] i64 with -100 behind each cloud's end, lengths [B] i32) -- what ULIP_PointBERT_partseg.forward_ragged(pc, onehot, lengths)
+    and a criterion with ignore_index = -100 take; `npoints` is not used.  lengths carries the batch's total row count as the host
+    integer `lengths._ppt_total` (validate_partseg passes it on, so no batch costs a device read).  One launch per batch
+    (cloud_prep; the part-seg recipe has no scale / shift draws); `.ragged` is True.  Rows of pc behind a cloud's end repeat its
+    last row.  No augmentation stages and no height column in this mode."""
 
     def __init__(self, cloud_set, batch_size, npoints, recipe, train, shuffle=True, drop_last=False, seed=0, draws="device", rank=0,
                  world_size=1, ahead=2, use_height=False, augment=None, ragged=False):
@@ -278,6 +286,13 @@ class DeviceBatchLoader:
                                  "that takes every cloud's own length)")
         # ragged: the set's lengths differ and the FPS launch takes them (ops.fps(lengths=)); a uniform set is today's path
         self._ragged = bool(ragged) and recipe in FPS_RECIPES and rows.min() != rows.max()
+        self.ragged = self._whole = bool(ragged) and recipe == "shapenetpart"          # whole shapes: batches carry lengths
+        if self._whole:
+            if self._aug_stages or self.use_height:
+                raise ValueError("recipe 'shapenetpart', ragged: no augmentation stages and no height column on whole shapes")
+            if cloud_set.points.shape[1] > MAX_NPOINTS:
+                raise ValueError(f"recipe 'shapenetpart', ragged: the set's clouds are padded to {cloud_set.points.shape[1]} rows, "
+                                 f"over the {MAX_NPOINTS} one batch row may have")
         self._exact = self._ragged and bool((rows == self.npoints).any())     # clouds of exactly npoints rows: no FPS for those
         if self._exact and recipe == "shapenet55":
             raise ValueError(f"recipe 'shapenet55', ragged: a cloud of exactly npoints = {self.npoints} rows takes random_sample's "
@@ -302,7 +317,7 @@ class DeviceBatchLoader:
         """which of ppt_cloud_draws' outputs the recipe itself needs"""
         part, sn = self.recipe == "shapenetpart", self.recipe == "shapenet55"
         translate = self.train and self.recipe in ("modelnet", "scanobjectnn")
-        return dict(start=self._fps_rows > 0, affine=translate, perm=translate or (sn and not self._fps_rows), sel=part)
+        return dict(start=self._fps_rows > 0, affine=translate, perm=translate or (sn and not self._fps_rows), sel=part and not self._whole)
 
     def plan(self):
         """The launches one batch takes, in order (names of ppt_amd.ops functions); numpy draws add one host-to-device copy instead
@@ -358,6 +373,15 @@ class DeviceBatchLoader:
         from .. import ops
         s, n = self.set, self.npoints
         part = self.recipe == "shapenetpart"
+        if self._whole:
+            # every stored row: rows behind a cloud's end come out as copies of its last row (cloud_prep clamps), their labels -100
+            rows_all = s.points.shape[1]
+            pc, seg = ops.cloud_prep(s.points, item, rows_all, lengths=s.lengths, seg_src=s.seg)
+            rows = s.rows(idx).astype(np.int32)
+            lens = torch.full((len(idx),), rows_all, dtype=torch.int32, device=pc.device) if s.lengths is None else s.lengths.index_select(0, item)
+            seg.masked_fill_(torch.arange(rows_all, device=pc.device).unsqueeze(0) >= lens.unsqueeze(1), -100)
+            lens._ppt_total = int(rows.sum())
+            return (pc, s.labels.index_select(0, item).to(torch.int32).view(-1, 1), seg, lens)
         want = self._recipe_draws()
         if self.draws == "numpy":
             d = self._host_draws(rs, idx)

@@ -150,21 +150,38 @@ def _bn_params(sd, p):
 # =================================================================================================
 # point branch
 # =================================================================================================
-def cloud_lengths(lengths, B, Nmax, device, least=1, what="lengths"):
+_NO_TOTAL = object()
+
+
+def cloud_lengths(lengths, B, Nmax, device, least=1, what="lengths", total_rows=_NO_TOTAL):
     """The per-cloud row counts of a padded batch [B, Nmax, 3] as the index kernels take them: [B] int32 on `device`.
     A host sequence / numpy array is validated (B entries, max(1, least) <= length <= Nmax) and uploaded; a device int32 tensor is
-    the caller's promise of the same and costs no host read (only its shape and dtype are looked at)."""
+    the caller's promise of the same and costs no host read (only its shape and dtype are looked at).
+    total_rows (given at all, None included): the caller works on PACKED rows and needs R = sum(lengths) on the host; the result
+    is then (lengths, R).  Host lengths give R for free.  For a device tensor R is the caller's total_rows (an int: the promise
+    that it is the sum); with total_rows=None the sum is read from the device here -- ONE host read, which waits for the
+    stream."""
+    want_total = total_rows is not _NO_TOTAL
     if torch.is_tensor(lengths) and lengths.is_cuda:
         if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
             raise ValueError(f"{what}: a device tensor must be int32 of shape ({B},), got {lengths.dtype} {tuple(lengths.shape)}")
-        return lengths.to(device).contiguous()
+        lengths = lengths.to(device).contiguous()
+        if not want_total:
+            return lengths
+        R = int(lengths.sum().item()) if total_rows is None else int(total_rows)
+        if not B * max(1, int(least)) <= R <= B * Nmax:
+            raise ValueError(f"{what}: total_rows = {R} cannot be the sum of {B} lengths in [{max(1, int(least))}, {Nmax}]")
+        return lengths, R
     host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths)
     if host.ndim != 1 or host.shape[0] != B or host.dtype.kind not in "iu":
         raise ValueError(f"{what}: expected {B} integers (one row count per cloud), got shape {host.shape} dtype {host.dtype}")
     lo = max(1, int(least))
     if host.min() < lo or host.max() > Nmax:
         raise ValueError(f"{what}: every cloud needs {lo} <= length <= Nmax = {Nmax} rows (got {int(host.min())} .. {int(host.max())})")
-    return torch.from_numpy(host.astype(np.int32)).to(device)
+    if want_total and total_rows is not None and int(total_rows) != int(host.sum()):
+        raise ValueError(f"{what}: total_rows = {int(total_rows)} but the lengths sum to {int(host.sum())}")
+    out = torch.from_numpy(host.astype(np.int32)).to(device)
+    return (out, int(host.sum())) if want_total else out
 
 
 def ragged_fps_start(lengths):

@@ -225,10 +225,13 @@ def finalize_partseg(records, batches, category2part, process_group=None):
     statement on the integer counts: batch accuracy `correct / (B * N)` in fp32, a part's IoU 1 when ground truth and prediction
     are both absent and else the int / int division in fp32, a cloud's figure the fp32 mean over its category's parts, category and
     overall figures torch.mean over fp32 tensors.  A category without a cloud gives NaN, and so does mean_class_iou then (the
-    reference's mean of an empty tensor); 'category_counts' lets a caller do otherwise."""
+    reference's mean of an empty tensor); 'category_counts' lets a caller do otherwise.
+    A ragged batch (PartsegMetrics.update(..., lengths=)) is listed as (B, Nmax, R), R the number of points that exist: R stands
+    where B * N stands for a uniform batch, in the batch accuracy and in the batch's mean loss."""
     rec = np.ascontiguousarray(np.asarray(records, dtype=np.int32).reshape(-1, ops.PARTSEG_REC))
     _raise_on_bad_labels(rec[:, 3], "clouds")
-    assert sum(b for b, _ in batches) == rec.shape[0], "batch sizes do not add up to the number of records"
+    batches = [(b[0], b[1], b[2] if len(b) > 2 else b[0] * b[1]) for b in batches]            # (B, N, points)
+    assert sum(b[0] for b in batches) == rec.shape[0], "batch sizes do not add up to the number of records"
     nonfinite = int(((rec[:, 3] & ops.METRIC_NONFINITE) != 0).sum())
     loss = rec[:, 4].copy().view(np.float32).astype(np.float64)
     by_start = {int(parts[0]): cat for cat, parts in category2part.items()}
@@ -237,14 +240,14 @@ def finalize_partseg(records, batches, category2part, process_group=None):
     count = 0
     correct_pts = total_pts = 0
     o = 0
-    for B, N in batches:
+    for B, N, points in batches:
         correct = int(rec[o:o + B, 2].sum())
-        acc = (torch.tensor(correct) / (B * N)).item()           # main_partseg.py:307-308: int64 tensor / int -> fp32
+        acc = (torch.tensor(correct) / points).item()            # main_partseg.py:307-308: int64 tensor / int -> fp32
         acc_sum += acc * B
-        loss_sum += float(loss[o:o + B].sum() / (B * N)) * B
+        loss_sum += float(loss[o:o + B].sum() / points) * B
         count += B
         correct_pts += correct
-        total_pts += B * N
+        total_pts += points
         for i in range(o, o + B):
             cat = by_start[int(rec[i, 0])]
             part_ious = [.0 for _ in range(len(category2part[cat]))]
@@ -290,7 +293,8 @@ def finalize_partseg(records, batches, category2part, process_group=None):
 
 class PartsegMetrics:
     """Part-segmentation metrics of one validation pass.  update(logits [B, N, P], labels [B, N]) queues one kernel on the
-    current stream and returns; result() -> {'acc', 'loss', 'mean_inst_iou', 'mean_class_iou', 'category_ious',
+    current stream and returns; update(..., lengths=) takes a padded ragged batch: cloud b is its first lengths[b] rows, nothing
+    behind them is read or counted (labels and logits there may be anything), accuracy and loss are over the points that exist; result() -> {'acc', 'loss', 'mean_inst_iou', 'mean_class_iou', 'category_ious',
     'category_counts', 'n', 'nonfinite_rows'}.  A cloud's category is the one its point 0's label belongs to
     (main_partseg.py:302, :326).  `nonfinite_rows` counts CLOUDS with a non-finite logit; their predictions are unspecified.
     A label outside [0, P) makes result() raise ValueError.  process_group: one collective of the per-category float64 IoU sums
@@ -308,12 +312,19 @@ class PartsegMetrics:
     def reset(self):
         self.records = _Records(ops.PARTSEG_REC)
 
-    def update(self, logits, labels):
+    def update(self, logits, labels, lengths=None, total_rows=None):
+        """lengths: a host sequence (validated: B entries, 1 <= length <= N) or a device int32 tensor [B]; for the latter pass
+        total_rows = sum(lengths) where the host knows it -- otherwise the sum is read from the device here, ONE host read."""
         if logits.dim() != 3 or logits.shape[2] != self.num_parts:
             raise ValueError(f"PartsegMetrics: logits {tuple(logits.shape)} for {self.num_parts} parts")
         logits, labels = _as_inputs(logits, labels)
         B, N, _ = logits.shape
         dev = logits.device
+        batch = (B, N)
+        if lengths is not None:
+            from . import engine
+            lengths, R = engine.cloud_lengths(lengths, B, N, dev, total_rows=total_rows)
+            batch = (B, N, R)
         if self._tables is None or self._tables[0].device != dev:
             # (host -> device, queued without waiting: the numpy arrays live as long as this object)
             self._tables = tuple(torch.from_numpy(t).to(dev, non_blocking=True) for t in (self.start, self.count))
@@ -321,8 +332,8 @@ class PartsegMetrics:
         if self._partial is None or self._partial.numel() < need or self._partial.device != dev:
             self._partial = torch.empty((need,), dtype=torch.float32, device=dev)
         ops.partseg_metrics(logits, labels, self.label_smoothing, self._tables[0], self._tables[1], self.max_parts,
-                            self.records.reserve(B, dev), self._partial)
-        self.records.commit(B, (B, N))
+                            self.records.reserve(B, dev), self._partial, lengths=lengths)
+        self.records.commit(B, batch)
 
     def result(self):
         return finalize_partseg(self.records.host(), self.records.batches, self.category2part, self.process_group)
@@ -372,7 +383,12 @@ def validate_partseg(test_loader, model, criterion, args):
     """Drop-in for main_partseg.validate (main_partseg.py:260-367): batch tuples (pc, cls_label, part_label, ...), the one-hot
     class label built on the device, model.eval(), no grad; `test_loader.dataset.category2part` gives the part ranges (a
     DeviceBatchLoader: pass `args.category2part`).  Returns {'acc', 'loss', 'mean_inst_iou', 'mean_class_iou'} with the reference's
-    meanings plus 'category_ious', 'category_counts', 'n', 'nonfinite_rows'."""
+    meanings plus 'category_ious', 'category_counts', 'n', 'nonfinite_rows'.
+    A loader that marks itself ragged (`test_loader.ragged`: DeviceBatchLoader(recipe="shapenetpart", ragged=True), whole shapes)
+    yields a fourth element, lengths [B] i32: it goes to model.forward_ragged and to the metrics, and every figure is over the
+    points that exist (part labels behind a cloud's end are never read).  The labels' padding is -100, the criterion's
+    default ignore_index (the only one _check_criterion accepts)."""
+    ragged = bool(getattr(test_loader, 'ragged', False))
     smoothing = _check_criterion(criterion)
     category2part = getattr(args, 'category2part', None)
     if category2part is None:
@@ -385,6 +401,12 @@ def validate_partseg(test_loader, model, criterion, args):
             pc = _to_device(inputs[0], args.gpu)
             cls_label = _to_device(inputs[1], args.gpu)
             part_label = _to_device(inputs[2], args.gpu)
+            if ragged:
+                lengths = _to_device(inputs[3], args.gpu)
+                total = getattr(inputs[3], '_ppt_total', None)          # the loader's host count: no device read per batch
+                part_pred = model.forward_ragged(pc, to_categorical(cls_label, num_shape_classes), lengths, total_rows=total)
+                metrics.update(part_pred, part_label, lengths=lengths, total_rows=total)
+                continue
             part_pred = model(pc, to_categorical(cls_label, num_shape_classes))
             metrics.update(part_pred, part_label)
     out = metrics.result()

@@ -885,16 +885,34 @@ class ULIP_WITH_IMAGE(nn.Module):
 
     def encode_pc(self, pc, cls_label=None, lengths=None):
         """ULIP_models.py:250-258.  lengths: a row count per cloud of a padded batch (recognition with PointBERT or PointNet++; the
-        encoder validates it: PointTransformer.forward) -- every other encoder and part-seg raise ValueError."""
+        encoder validates it: PointTransformer.forward) -- every other encoder and part-seg raise ValueError.  Part-seg on a
+        ragged batch goes through encode_pc_ragged / forward_ragged."""
         if self.task == 'partseg':
             if lengths is not None:
-                raise ValueError("part-seg takes no ragged input (lengths=): the decoder works over all B*N input rows")
+                raise ValueError("part-seg takes no lengths= here (this call works over all B*N input rows): a ragged batch goes "
+                                 "through forward_ragged(pc, cls_label, lengths) / encode_pc_ragged, which run on the rows that exist")
             pc_feat = self.point_encoder(pc, cls_label)
         else:
             pc_feat = self.point_encoder(pc) if lengths is None else self.point_encoder(pc, lengths=lengths)
         wt = engine._f32_cache(self._cache()).get(self.pc_projection, "wt")     # [embed, feat]
         lead = pc_feat.shape[:-1]
         return matmul_nt(pc_feat.reshape(-1, pc_feat.shape[-1]), wt, self._head_precision()).view(*lead, -1)
+
+    def encode_pc_ragged(self, pc, cls_label, lengths, total_rows=None):
+        """part-seg: encode_pc for a padded ragged batch -> [B,N,embed] with zero rows behind every cloud's end (lengths, total_rows:
+        as forward_ragged)."""
+        from ..autograd import unpack_rows
+        emb, offsets = self._encode_pc_packed(pc, cls_label, lengths, total_rows)
+        return unpack_rows(emb, offsets, pc.shape[1])
+
+    def _encode_pc_packed(self, pc, cls_label, lengths, total_rows=None):
+        """part-seg on a padded ragged batch -> (point embeddings [R,embed] on PACKED rows, offsets [B+1] i32): the decoder's tail
+        and the projection run on the R = sum(lengths) rows that exist."""
+        if not hasattr(self.point_encoder, "forward_packed"):
+            raise ValueError(f"{type(self.point_encoder).__name__} takes no ragged input (lengths=)")
+        pc_feat, offsets = self.point_encoder.forward_packed(pc, cls_label, lengths, total_rows=total_rows)
+        wt = engine._f32_cache(self._cache()).get(self.pc_projection, "wt")     # [embed, feat]
+        return matmul_nt(pc_feat, wt, self._head_precision()), offsets
 
     TEXT_CALIBRATION_THRESHOLD = 1e-2
 
@@ -983,17 +1001,34 @@ class ULIP_WITH_IMAGE(nn.Module):
             self._text_stream = graphs.shared_text_stream()
         return self._text_stream
 
+    def forward_ragged(self, pc, cls_label, lengths, total_rows=None):
+        """Part-seg on whole shapes: pc [B,N,3] padded, cloud b its first lengths[b] rows (a host sequence, validated: B entries,
+        group_size <= length <= N; or a device int32 tensor [B], taken on trust) -> logits [B,N,C] with ZERO rows behind every
+        cloud's end.  The decoder's tail, the projection and the product with the text features run on the R = sum(lengths) packed
+        rows (PointTransformer_partseg.forward_packed); nothing behind a cloud's end is read.  For the criterion pad the labels with
+        -100 (nn.CrossEntropyLoss's default ignore_index): the loss is then the mean over the rows that exist and a plain
+        loss.backward() trains.  lengths as a device tensor costs one host read of its sum here, unless total_rows = sum(lengths)
+        is given.  (forward(pc, cls_label, lengths=...) keeps refusing part-seg, as forward_loss and Trainer.step do.)"""
+        if self.task != 'partseg':
+            raise ValueError("forward_ragged is the part-seg call; recognition takes forward(pc, lengths=...)")
+        pe = self.point_encoder
+        lengths, rows = engine.cloud_lengths(lengths, pc.shape[0], pc.shape[1], pc.device, least=getattr(pe, "group_size", 1),
+                                             total_rows=total_rows)
+        with gradscale.rows(rows):                   # the rows the criterion averages over (see forward)
+            return self._forward(pc, cls_label, lengths, total_rows=rows)
+
     def forward(self, pc, cls_label=None, lengths=None):
         """ULIP_models.py:260-283 -> logits [B,C] (partseg: [B,N,C]).  lengths: see encode_pc."""
         # the rows the caller's criterion will average over: fixes the power-of-two scale of every 16-bit backward stage created
         # by this forward (ppt_amd/gradscale.py) -- a plain `loss.backward()` (main_cls.py:197, main_partseg.py:214) is then
         # scaled and un-scaled inside the nodes
         if lengths is not None and self.task == 'partseg':
-            raise ValueError("part-seg takes no ragged input (lengths=): the decoder works over all B*N input rows")
+            raise ValueError("part-seg takes no lengths= here (this call works over all B*N input rows): a ragged batch goes "
+                             "through forward_ragged(pc, cls_label, lengths), which runs on the rows that exist")
         with gradscale.rows(pc.shape[0] * (pc.shape[1] if self.task == 'partseg' else 1)):
             return self._forward(pc, cls_label, lengths)
 
-    def _forward(self, pc, cls_label=None, lengths=None):
+    def _forward(self, pc, cls_label=None, lengths=None, total_rows=None):
         cur = torch.cuda.current_stream()
         side = None
         if self.overlap_text_tower and pc.is_cuda:
@@ -1011,7 +1046,11 @@ class ULIP_WITH_IMAGE(nn.Module):
             pe.inputs_vouched = bool(self.eval_inputs_ready)     # (else: only tensors that carry their copy event run ahead)
         try:
             with self._tower_room():
-                pc_embed = self.encode_pc(pc, cls_label, lengths) if self.task == 'partseg' else self.encode_pc(pc, lengths=lengths)
+                offsets = None
+                if self.task == 'partseg' and lengths is not None:
+                    pc_embed, offsets = self._encode_pc_packed(pc, cls_label, lengths, total_rows)           # [R,embed]
+                else:
+                    pc_embed = self.encode_pc(pc, cls_label, lengths) if self.task == 'partseg' else self.encode_pc(pc, lengths=lengths)
         finally:
             if ahead:
                 pe.group_ahead = None
@@ -1030,6 +1069,9 @@ class ULIP_WITH_IMAGE(nn.Module):
             logits = logit_scale * matmul_nt(pc_embed.reshape(-1, pc_embed.shape[-1]), text_embed, hp)
         else:
             logits = matmul_nt((logit_scale * pc_embed).reshape(-1, pc_embed.shape[-1]), text_embed, hp)
+        if offsets is not None:
+            from ..autograd import unpack_rows
+            return unpack_rows(logits, offsets, pc.shape[1])                # [R,C] -> [B,N,C], zero rows behind every cloud's end
         return logits.view(*lead, -1)
 
     def forward_loss(self, pc, labels, smoothing, lengths=None):

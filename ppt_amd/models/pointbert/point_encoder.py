@@ -490,6 +490,54 @@ class PointTransformer(nn.Module):
         return _PointEncoderFn.apply(self, pts, start, dp, tier, names, lengths, *[sd[n] for n in names])
 
 
+def _partseg_forward_packed(self, pts, cls_label, lengths, total_rows=None):
+    """PointTransformer_partseg on a padded ragged batch -> (features [R,128] on PACKED rows, offsets [B+1] i32), R =
+    sum(lengths).  Eager: no hipGraph and no ahead stage -- the row counts are data the captured launches would freeze.  The
+    three FPS walks (one ragged launch where they are one launch) and the kNN grouping take the lengths; the frozen backbone,
+    propagation_1/2 and dgcnn_pro_1/2 work on the fixed anchor sets and run as ever; propagation_0, conv1 / bn1 and the dropout
+    work on the R rows that exist, so their BatchNorm statistics never see a padding row.  Nothing behind row lengths[b]-1 of
+    pts[b] is read.  lengths as a device int32 tensor: pass total_rows, or its sum is read from the device once."""
+    from ...autograd import conv_bn_relu_rows
+    pts = pts.contiguous().float()
+    B, N, _ = pts.shape
+    dev = pts.device
+    lengths, R = engine.cloud_lengths(lengths, B, N, dev, least=self.group_size, total_rows=total_rows)
+    offsets = ops.cloud_offsets(lengths)
+    if self.fps_start is not None:
+        s0, s1, s2 = (t.to(dev).contiguous() for t in self.fps_start)
+    else:                                            # three independent random starts, each below its cloud's length
+        s0, s1, s2 = (engine.ragged_fps_start(lengths) for _ in range(3))
+    with torch.no_grad():
+        if self.num_group == 512:
+            _, ctr = ops.fps(pts.repeat(3, 1, 1), 512, torch.cat([s0, s1, s2]), lengths=lengths.repeat(3))
+            center, c1, c2 = ctr[:B].contiguous(), ctr[B:2 * B].contiguous(), ctr[2 * B:, :256].contiguous()
+        else:
+            _, center = ops.fps(pts, self.num_group, s0, lengths=lengths)
+            _, c1 = ops.fps(pts, 512, s1, lengths=lengths)
+            _, c2 = ops.fps(pts, 256, s2, lengths=lengths)
+        _, nbhd = ops.knn_group(pts, center, self.group_size, want_idx=False, lengths=lengths)
+        dp = self._draw_drop_path(B, dev)
+        feats, center = engine.point_encoder_forward(self._live_state(), "", self._cache(), None, None, dp, self.training, 0,
+                                                     self._cfg(), fetch=(3, 7, 11), grouped=(nbhd, center))
+        center = center.contiguous()
+    if self.decoder_gate is not None:
+        if pts.is_cuda:
+            torch.cuda.current_stream().wait_event(self.decoder_gate)
+        self.decoder_gate = None
+    f2 = self.propagation_2.forward_rows(c2, center, c2, feats[1])
+    f1 = self.propagation_1.forward_rows(c1, center, c1, feats[0])
+    f2 = self.dgcnn_pro_2.forward_rows(center, feats[2], c2, f2)
+    f1 = self.dgcnn_pro_1.forward_rows(c2, f2, c1, f1)
+    # [one-hot(16) | xyz(3) | interpolated]: the class row and the padded cloud go into the kernel as they are
+    f0 = self.propagation_0.forward_rows_packed(pts, c1, cls_label.float().reshape(B, 16).contiguous(), pts, f1, lengths, offsets, R)
+    y = conv_bn_relu_rows(f0, self.conv1, self.bn1, self.training, self._dec_precision)           # [R,128]
+    if self.dropout_mask is not None:
+        y = y * ops.pack_rows(self.dropout_mask.to(dev).contiguous(), offsets, R)
+    elif self.training:
+        y = self.drop1(y)
+    return y, offsets
+
+
 class PointTransformer_partseg(nn.Module):
     """point_encoder.py:260-420.  forward(pts [B,N,3], cls_label one-hot [B,16]) -> per-point features [B,N,128].
     The PointBERT backbone (tokenizer + 12 blocks, frozen in PPT: ULIP_models.py:550-565) runs on the engine
@@ -583,11 +631,17 @@ class PointTransformer_partseg(nn.Module):
         return super()._apply(fn, *a, **k)
 
     load_model_from_ckpt = _load_model_from_ckpt
+    forward_packed = _partseg_forward_packed
 
     def forward(self, pts, cls_label, lengths=None):
+        """pts [B,N,3], cls_label [B,16] -> per-point features [B,N,128].  lengths: a row count per cloud of a padded batch
+        (engine.cloud_lengths; every cloud needs group_size rows, one shorter than the 512 / 256 anchors repeats picks as that
+        cloud alone does): the N-dependent tail of the decoder runs on the packed rows that exist (forward_packed), the result is
+        unpacked to [B,N,128] with zero rows behind every cloud's end."""
         if lengths is not None:
-            raise ValueError("PointTransformer_partseg: no ragged input (lengths=): its decoder convolves and batch-normalises over "
-                             "all B*N input rows, so padding rows would enter the statistics")
+            from ...autograd import unpack_rows
+            y, offsets = self.forward_packed(pts, cls_label, lengths)
+            return unpack_rows(y, offsets, pts.shape[1])
         from ...autograd import conv_bn_relu_rows
         pts = pts.contiguous().float()
         B, N, _ = pts.shape

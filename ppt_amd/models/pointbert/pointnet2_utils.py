@@ -54,6 +54,22 @@ class PointNetFeaturePropagation(nn.Module):
             with torch.no_grad():
                 idx, _, d = ops.knn_group(xyz2.contiguous().float(), xyz1.contiguous().float(), 3, want_nbhd=False, want_dist=True)
             return feature_propagation(self, points1, points2, idx, d, self.precision)
+        return self._forward_rows_slow(xyz1, xyz2, points1, points2)
+
+    def forward_rows_packed(self, xyz1, xyz2, cloud_cols, points1, points2, lengths, offsets, total_rows):
+        """forward_rows for the targets of a ragged batch: xyz1 [B,Nmax,3] padded, cloud b its first lengths[b] rows (lengths [B]
+        i32 on the device, offsets [B+1] their prefix sum, total_rows = R their sum); xyz2 [B,S,3] / points2 [B,S,D2] the
+        sources; the points1 columns are [cloud_cols[b] | points1[b, n]] (cloud_cols [B,Dc] | None, points1 [B,Nmax,Dp] | None
+        padded) -> PACKED rows [R, mlp[-1]].  Nothing behind a cloud's end is read; the BatchNorm statistics are over the R rows."""
+        assert xyz2.shape[1] >= 3 and len(self.mlp_convs) == 2
+        with torch.no_grad():
+            idx, _, d = ops.knn_group(xyz2.contiguous().float(), xyz1.contiguous().float(), 3, want_nbhd=False, want_dist=True,
+                                      query_lengths=lengths, query_offsets=offsets, total_rows=total_rows)
+        return feature_propagation(self, points1, points2, idx, d, self.precision, packed=(cloud_cols, offsets))
+
+    def _forward_rows_slow(self, xyz1, xyz2, points1, points2):
+        B, N, _ = xyz1.shape
+        S = xyz2.shape[1]
         if S == 1:
             interpolated = points2.repeat(1, N, 1)
         else:

@@ -131,12 +131,50 @@ def fps(xyz, M, start, lengths=None):
     return idx, ctr
 
 
-def knn_group(xyz, center, k, want_idx=True, want_nbhd=True, want_dist=False, lengths=None):
+def cloud_offsets(lengths):
+    """lengths [B] i32 (device) -> offsets [B+1] i32: the exclusive prefix sum, cloud b owning packed rows offsets[b] ..
+    offsets[b+1]-1 (the layout of every *_packed function below; include/ppt_hip.h)."""
+    _chk(lengths, torch.int32, "lengths")
+    off = torch.zeros(lengths.numel() + 1, dtype=torch.int32, device=lengths.device)
+    off[1:] = torch.cumsum(lengths, 0, dtype=torch.int32)
+    return off
+
+
+def _chk_offsets(offsets, B):
+    _chk(offsets, torch.int32, "offsets")
+    if tuple(offsets.shape) != (B + 1,):
+        raise RuntimeError(f"offsets: expected shape ({B + 1},), got {tuple(offsets.shape)}")
+
+
+def knn_group(xyz, center, k, want_idx=True, want_nbhd=True, want_dist=False, lengths=None, query_lengths=None,
+              query_offsets=None, total_rows=None):
     """H2.  xyz [B,N,3], center [B,G,3] -> (nbr_idx [B,G,k] i64, neighborhood [B,G,k,3] f32[, dist [B,G,k] f32]).
-    lengths [B] i32 (device): per-cloud row counts, every one >= k (ppt_knn_group_ragged_f32)."""
+    lengths [B] i32 (device): per-cloud row counts, every one >= k (ppt_knn_group_ragged_f32).
+    query_lengths [B] i32 (device): cloud b has query_lengths[b] centres, rows 0 .. of its [G,3] slab; the outputs are then PACKED
+    rows, [R,k] / [R,k,3] / [R,k] with R = total_rows = sum(query_lengths) and query_offsets [B+1] i32 their prefix sum (computed
+    here when None) -- ppt_knn_group_packed_f32; cloud b's rows are those of knn_group on that cloud's queries alone."""
     _chk(xyz, torch.float32, "xyz"); _chk(center, torch.float32, "center")
     B, N, _ = xyz.shape
     G = center.shape[1]
+    if query_lengths is not None:
+        _chk_lengths(query_lengths, B)
+        if lengths is not None:
+            _chk_lengths(lengths, B)
+        if query_offsets is None:
+            query_offsets = cloud_offsets(query_lengths)
+        _chk_offsets(query_offsets, B)
+        R = int(total_rows)
+        idx = torch.empty((R, k), dtype=torch.int64, device=xyz.device) if want_idx else None
+        nb = torch.empty((R, k, 3), dtype=torch.float32, device=xyz.device) if want_nbhd else None
+        nd = torch.empty((R, k), dtype=torch.float32, device=xyz.device) if want_dist else None
+        if profiler is not None:
+            profiler.begin("knn_group_packed", float(B) * 12 * N + float(R) * (12 + 8 * k + 12 * k))
+        _lib.check(_lib.lib().ppt_knn_group_packed_f32(_p(xyz), _p(center), B, N, G, k, _p(lengths), _p(query_lengths),
+                                                       _p(query_offsets), R, _p(idx), _p(nb), _p(nd), _stream()),
+                   "ppt_knn_group_packed_f32")
+        if profiler is not None:
+            profiler.end()
+        return (idx, nb, nd) if want_dist else (idx, nb)
     idx = torch.empty((B, G, k), dtype=torch.int64, device=xyz.device) if want_idx else None
     nb = torch.empty((B, G, k, 3), dtype=torch.float32, device=xyz.device) if want_nbhd else None
     if profiler is not None:
@@ -957,6 +995,85 @@ def scatter_rows_bwd(idx, weight, d_rows, col_off, rows_div, S, C):
     return out
 
 
+def three_nn_interp_packed(cloud_cols, points1, points2, idx, dist, offsets, out_dtype, mult):
+    """ppt_three_nn_interp_packed_fwd: three_nn_interp on the R packed rows of a ragged batch.  idx / dist [R,3] (knn_group with
+    query_lengths), points2 [B,S,D2], offsets [B+1] i32; the points1 columns are [cloud_cols[b] | points1[b, n]] with cloud_cols
+    [B,Dc] | None one row per cloud and points1 [B,Nmax,Dp] | None a PADDED slab -- neither is ever packed.
+    -> (rows [R, ld] in out_dtype, normalised weights [R,3] f32)."""
+    _chk(points2, torch.float32, "points2"); _chk(idx, torch.int64, "idx"); _chk(dist, torch.float32, "dist")
+    _chk(points1, torch.float32, "points1"); _chk(cloud_cols, torch.float32, "cloud_cols")
+    R = idx.shape[0]
+    B, S, D2 = points2.shape
+    _chk_offsets(offsets, B)
+    assert tuple(idx.shape) == (R, 3) and tuple(dist.shape) == (R, 3)
+    Dc = 0 if cloud_cols is None else cloud_cols.shape[1]
+    Dp = 0 if points1 is None else points1.shape[2]
+    assert cloud_cols is None or cloud_cols.shape[0] == B
+    assert points1 is None or points1.shape[0] == B
+    assert points1 is not None or cloud_cols is None, "the slab gives the row stride: cloud_cols alone is not supported"
+    Nmax = points1.shape[1] if points1 is not None else R
+    ld = (Dc + Dp + D2 + mult - 1) // mult * mult
+    rows = torch.empty((R, ld), dtype=out_dtype, device=points2.device)
+    w = torch.empty((R, 3), dtype=torch.float32, device=points2.device)
+    if profiler is not None:
+        profiler.begin("three_nn_interp_packed", float(R) * (36 + 12 * D2 + ld * rows.element_size() + 12))
+    _lib.check(_lib.lib().ppt_three_nn_interp_packed_fwd(_p(cloud_cols), Dc, _p(points1), Dp, _p(points2), D2, _p(idx), _p(dist),
+                                                         _p(offsets), B, Nmax, R, S, _p(rows), dtype_code(rows), ld, _p(w),
+                                                         _stream()), "ppt_three_nn_interp_packed_fwd")
+    if profiler is not None:
+        profiler.end()
+    return rows, w
+
+
+def scatter_rows_packed_bwd(idx, weight, d_rows, col_off, rows_div, offsets, S, C):
+    """ppt_scatter_rows_packed_bwd: scatter_rows_bwd for packed rows.  idx [R * rows_div] i64 (rows_div entries per packed row),
+    weight like it | None, d_rows [R, ld] f32, offsets [B+1] i32 -> d_src [B,S,C] f32; cloud b's sources take the entries of its
+    own rows only, in ascending order."""
+    _chk(idx, torch.int64, "idx"); _chk(weight, torch.float32, "weight"); _chk(d_rows, torch.float32, "d_rows")
+    B = offsets.numel() - 1
+    _chk_offsets(offsets, B)
+    R = d_rows.shape[0]
+    assert idx.numel() == R * rows_div and (weight is None or weight.numel() == R * rows_div)
+    out = torch.empty((B, S, C), dtype=torch.float32, device=d_rows.device)
+    _lib.check(_lib.lib().ppt_scatter_rows_packed_bwd(_p(idx), _p(weight), _p(d_rows), d_rows.shape[1], col_off, _p(offsets), B, R,
+                                                      rows_div, S, C, _p(out), _stream()), "ppt_scatter_rows_packed_bwd")
+    return out
+
+
+def pack_rows(padded, offsets, total_rows):
+    """padded [B, Nmax, ...] -> packed [R, ...]: cloud b's first offsets[b+1] - offsets[b] rows, in order; nothing behind them is
+    read (ppt_pack_rows; any dtype).  The backward of unpack_rows."""
+    assert padded.is_contiguous() and padded.dim() >= 2
+    B, Nmax = padded.shape[:2]
+    _chk_offsets(offsets, B)
+    R = int(total_rows)
+    out = torch.empty((R,) + tuple(padded.shape[2:]), dtype=padded.dtype, device=padded.device)
+    row_bytes = out[0].numel() * out.element_size()
+    if profiler is not None:
+        profiler.begin("pack_rows", 2.0 * R * row_bytes)
+    _lib.check(_lib.lib().ppt_pack_rows(_p(padded), _p(out), _p(offsets), B, Nmax, R, row_bytes, _stream()), "ppt_pack_rows")
+    if profiler is not None:
+        profiler.end()
+    return out
+
+
+def unpack_rows(packed, offsets, Nmax):
+    """packed [R, ...] -> padded [B, Nmax, ...] with ZERO rows behind every cloud's end (ppt_unpack_rows; any dtype).  The
+    backward of pack_rows."""
+    assert packed.is_contiguous() and packed.dim() >= 1
+    B = offsets.numel() - 1
+    _chk_offsets(offsets, B)
+    R = packed.shape[0]
+    out = torch.empty((B, int(Nmax)) + tuple(packed.shape[1:]), dtype=packed.dtype, device=packed.device)
+    row_bytes = packed[0].numel() * packed.element_size()
+    if profiler is not None:
+        profiler.begin("unpack_rows", float(R + B * int(Nmax)) * row_bytes)
+    _lib.check(_lib.lib().ppt_unpack_rows(_p(packed), _p(out), _p(offsets), B, int(Nmax), R, row_bytes, _stream()), "ppt_unpack_rows")
+    if profiler is not None:
+        profiler.end()
+    return out
+
+
 def sum_groups(x, k):
     """x [G*k, C] f32 -> [G, C]: sums of each k consecutive rows."""
     _chk(x, torch.float32, "x")
@@ -1347,16 +1464,28 @@ def partseg_metrics_chunks(N):
     return _lib.lib().ppt_partseg_metrics_chunks(int(N))
 
 
-def partseg_metrics(logits, labels, smoothing, part_start, part_count, max_parts, records, partial):
+def partseg_metrics(logits, labels, smoothing, part_start, part_count, max_parts, records, partial, lengths=None):
     """logits [B, N, P] f32, labels [B, N] i64, part_start / part_count [P] i32 (per part id: its category's first part and
     number of parts; max_parts = the largest count) -> records [B, 32] i32 (a caller-owned slice): per cloud the category's range,
     the correct points, the loss sum and the per-part |gt|, |pred|, |gt and pred| (ppt_partseg_metrics; layout: include/ppt_hip.h).
-    partial: scratch of at least B * partseg_metrics_chunks(N) f32."""
+    partial: scratch of at least B * partseg_metrics_chunks(N) f32.
+    lengths [B] i32 (device): N is the row stride and cloud b its first lengths[b] rows -- nothing behind them is counted or
+    read, and the record is the one of that cloud alone (ppt_partseg_metrics_ragged)."""
     _chk(logits, torch.float32, "logits"); _chk(labels, torch.int64, "labels"); _chk(records, torch.int32, "records")
     _chk(part_start, torch.int32, "part_start"); _chk(part_count, torch.int32, "part_count"); _chk(partial, torch.float32, "partial")
     B, N, P = logits.shape
     assert labels.shape == (B, N) and records.shape == (B, PARTSEG_REC) and part_start.numel() == P and part_count.numel() == P
     assert partial.numel() >= B * partseg_metrics_chunks(N)
+    if lengths is not None:
+        _chk_lengths(lengths, B)
+        if profiler is not None:
+            profiler.begin("partseg_metrics_ragged", float(B) * N * (4 * P + 8))
+        _lib.check(_lib.lib().ppt_partseg_metrics_ragged(_p(logits), _p(labels), _p(lengths), float(smoothing), B, N, P,
+                                                         _p(part_start), _p(part_count), int(max_parts), _p(records), _p(partial),
+                                                         _stream()), "ppt_partseg_metrics_ragged")
+        if profiler is not None:
+            profiler.end()
+        return
     _lib.check(_lib.lib().ppt_partseg_metrics(_p(logits), _p(labels), float(smoothing), B, N, P, _p(part_start), _p(part_count),
                                               int(max_parts), _p(records), _p(partial), _stream()), "ppt_partseg_metrics")
 
@@ -1381,14 +1510,21 @@ def train_meter_cls(logits, labels, loss, rec, weight=1.0, metered=True):
                                               _stream()), "ppt_train_meter_cls")
 
 
-def train_meter_partseg(logits, labels, loss, part_start, part_count, rec, scratch, weight=1.0, metered=True):
+def train_meter_partseg(logits, labels, loss, part_start, part_count, rec, scratch, weight=1.0, metered=True, lengths=None):
     """One training step of main_partseg.py:218-243 folded into rec [8] f64: logits [B, N, P] f32, labels [B, N] i64, part_start /
     part_count [P] i32 as for partseg_metrics; scratch [4] i32, all zero before the first call and after every call
-    (ppt_train_meter_partseg)."""
+    (ppt_train_meter_partseg).  lengths [B] i32 (device): only rows < lengths[b] are counted or read and the accuracy's
+    denominator is sum(lengths) (ppt_train_meter_partseg_ragged)."""
     _meter_args(logits, labels, loss, rec)
     _chk(part_start, torch.int32, "part_start"); _chk(part_count, torch.int32, "part_count"); _chk(scratch, torch.int32, "scratch")
     B, N, P = logits.shape
     assert labels.shape == (B, N) and part_start.numel() == P and part_count.numel() == P and scratch.numel() >= METER_SCRATCH
+    if lengths is not None:
+        _chk_lengths(lengths, B)
+        _lib.check(_lib.lib().ppt_train_meter_partseg_ragged(_p(logits), _p(labels), _p(lengths), _p(loss), B, N, P, _p(part_start),
+                                                             _p(part_count), float(weight), int(bool(metered)), _p(rec),
+                                                             _p(scratch), _stream()), "ppt_train_meter_partseg_ragged")
+        return
     _lib.check(_lib.lib().ppt_train_meter_partseg(_p(logits), _p(labels), _p(loss), B, N, P, _p(part_start), _p(part_count),
                                                   float(weight), int(bool(metered)), _p(rec), _p(scratch), _stream()),
                "ppt_train_meter_partseg")

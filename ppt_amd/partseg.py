@@ -49,12 +49,16 @@ def run_partseg(model, train_set, test_set, args, trainer=None):
     and the three best figures as :117-120 track them; on a new best checkpoint_payload(..., partseg=True, best_mean_class_iou=...,
     best_mean_inst_iou=...) written by rank 0.
     -> one dict per epoch with the reference's log_stats keys (:145-152): train_loss, train_acc, train_lr, train_logit_scale,
-    test_<key> for every key validate_partseg returns, best_test_acc, best_mean_inst_iou, best_mean_class_iou, best_epoch."""
+    test_<key> for every key validate_partseg returns, best_test_acc, best_mean_inst_iou, best_mean_class_iou, best_epoch.
+    args.whole_shapes (--whole_shapes): the TEST loader yields every stored row of every shape (DeviceBatchLoader(ragged=True)) and
+    acc / mean_inst_iou / mean_class_iou are over the points that exist, not over a 2048-point resample with duplicates; training
+    stays on the resampled batches."""
     category2part = getattr(args, "category2part", None)
     if category2part is None:
         raise ValueError("run_partseg: args.category2part ({category: [part ids]}) is needed")
     num_shape_classes = len(category2part)
-    train_loader, test_loader = _loaders(train_set, test_set, args, "shapenetpart", DEFAULTS)
+    train_loader, test_loader = _loaders(train_set, test_set, args, "shapenetpart", DEFAULTS,
+                                         whole_shapes=bool(getattr(args, "whole_shapes", False)))
     criterion = torch.nn.CrossEntropyLoss(label_smoothing=float(_arg(args, "label_smoothing")))      # main_partseg.py:51
     if trainer is None:
         trainer = _trainer(model, args, len(train_loader), DEFAULTS)
@@ -112,6 +116,8 @@ def parse_args(argv=None):
     add_common_arguments(ap, DEFAULTS)
     ap.add_argument("--model", default="ULIP_PointBERT_partseg")
     ap.add_argument("--dataset_name", default="shapenetpart")
+    ap.add_argument("--whole_shapes", action="store_true",
+                    help="validate on every stored point of every test shape (ragged batches) instead of a resample to --npoints")
     args = ap.parse_args(argv)
     args.betas = tuple(args.betas)
     args.task, args.evaluate_3d, args.rank, args.world_size, args.recipe = "partseg", False, 0, 1, "shapenetpart"

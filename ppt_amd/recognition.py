@@ -39,14 +39,19 @@ def _arg(args, name, defaults=DEFAULTS):
     return getattr(args, name, defaults[name])
 
 
-def _loaders(train_set, test_set, args, recipe, defaults):
+def _loaders(train_set, test_set, args, recipe, defaults, whole_shapes=False):
     batch_size, npoints, seed, rank, world = (int(_arg(args, k, defaults)) for k in ("batch_size", "npoints", "seed", "rank", "world_size"))
     kw = dict(drop_last=False, seed=seed, rank=rank, world_size=world, use_height=bool(_arg(args, "use_height", defaults)))
     # main_cls.py:74-87; the test split is walked in its stored order, as run_fewshot walks it (the reference shuffles it too, which
     # moves no figure but the order of the per-class table)
     # a set that carries lengths may hold clouds of differing length: the loader's one FPS launch then takes them (ragged=True)
-    return (DeviceBatchLoader(train_set, batch_size, npoints, recipe, train=True, shuffle=True, ragged=train_set.lengths is not None, **kw),
-            DeviceBatchLoader(test_set, batch_size, npoints, recipe, train=False, shuffle=False, ragged=test_set.lengths is not None, **kw))
+    # part-seg: its sets are resampled to npoints rows whatever their lengths; whole_shapes puts the TEST loader into the
+    # whole-shape mode (every stored row, batches that carry lengths) and leaves training on the resampled batches
+    part = recipe == "shapenetpart"
+    return (DeviceBatchLoader(train_set, batch_size, npoints, recipe, train=True, shuffle=True,
+                              ragged=train_set.lengths is not None and not part, **kw),
+            DeviceBatchLoader(test_set, batch_size, npoints, recipe, train=False, shuffle=False,
+                              ragged=bool(whole_shapes) if part else test_set.lengths is not None, **kw))
 
 
 def _trainer(model, args, n_batches, defaults):
