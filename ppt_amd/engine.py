@@ -393,7 +393,7 @@ def vit_block_forward(sd, p, wc, x, pos, B, Tn, heads, dp1, dp2, save=None, pos_
 def tokenize_points(sd, p, wc, pc, fps_start, bn_train, cfg, update_running=True, grouped=None):
     """The part of PointTransformer.forward in front of the blocks (point_encoder.py:234-249): Group (FPS + kNN), the
     mini-PointNet encoder, reduce_dim, cls token / cls_pos and pos_embed -> (x2, pos2), both [B*Tn, D] fp32 (Tn = G + 1).
-    A function of the input cloud and frozen weights alone: train.Trainer can run it ahead of the step (PointTransformer._group_ahead)."""
+    A function of the input cloud and frozen weights alone: train.Trainer can run it ahead of the step (as a graphs.AheadStage)."""
     G, D = cfg["num_group"], cfg["trans_dim"]
     Tn = G + 1
     # grouped = (nbhd, center): Group.forward was already run (ahead of the step, on its own stream)

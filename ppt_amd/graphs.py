@@ -13,6 +13,8 @@ import os
 
 import torch
 
+from . import engine, ops
+
 enabled = os.environ.get("PPT_HIP_GRAPHS", "1") != "0"      # PPT_HIP_GRAPHS=0: eager launches only (per-dispatch counters)
 WARMUP_CALLS = 2
 
@@ -168,12 +170,79 @@ class AheadStage:
         self.free[slot] = torch.cuda.current_stream().record_event()
 
 
+class FrozenTower:
+    """Mixin (in front of nn.Module) of the point encoders that are frozen in every PPT configuration -- Pointnet2_Msg / _Ssg,
+    PointMLP's Model, PointNeXt's BaseCls: their knobs, their caches and the ONE place that decides how a forward's launches run --
+    eagerly, replayed from a hipGraph once the shape is warmed up, or replayed with the input-only grouping stage on the grouping
+    stream, one step ahead (AheadStage).  The model's forward keeps its argument checks, RNG draws and key, and calls dispatch()."""
+
+    def _init_tower(self, fps_start=True):
+        self.precision = torch.bfloat16
+        if fps_start:
+            self.fps_start = None
+        self.dropout_masks = None
+        self._wc = None
+        self._sd = None
+        self._graphs = GraphCache()
+        self.use_hip_graphs = True
+        self.group_ahead = None            # stream for the grouping stage of the next iteration (train.Trainer.inputs_ready)
+        self._ahead = AheadStage()
+
+    def _apply(self, fn, *a, **k):
+        self._sd = None
+        if hasattr(self, "_graphs"):       # (nn.Module.__init__ paths come through here before _init_tower ran)
+            self._graphs.clear()
+        return super()._apply(fn, *a, **k)
+
+    def load_state_dict(self, *a, **k):
+        self._sd, self._wc = None, None
+        if hasattr(self, "_graphs"):
+            self._graphs.clear()
+        return super().load_state_dict(*a, **k)
+
+    def _state(self, anchor, dtype=None):
+        """-> (state dict of live parameters, WeightCache).  The table is re-read when `anchor` (one weight of the model) is another
+        object, the cache re-made when the operand format (default: self.precision) changes."""
+        dtype = self.precision if dtype is None else dtype
+        if self._wc is None or self._wc.dtype != dtype:
+            self._wc = engine.WeightCache(dtype)
+        if self._sd is None or self._sd[1] is not anchor:
+            self._sd = (self.state_dict(keep_vars=True), anchor)
+        return self._sd[0], self._wc
+
+    def dispatch(self, key, inputs, masks, run, group=None, carry=()):
+        """The feature of run(inputs, masks, grouped), by the cheapest means that is allowed now.
+        inputs: the cloud first, then what else the whole tower reads (FPS starts); masks: tuple of dropout masks or None.
+        run(inputs, masks, None) is the whole tower; run(carry, masks, grouped) the tower behind its grouping stage, `carry` being the
+        inputs it still reads beside the grouped tensors.  group = (stage key, gfn, stage inputs) as for AheadStage.run: used when
+        `group_ahead` names a stream.  Graph keys: `key`, key + ("grouped",), stage key + (slot,)."""
+        if not (inputs[0].is_cuda and self.use_hip_graphs and ops.profiler is None and self._graphs.ready(key)):
+            return run(inputs, masks, None)
+        if group is not None and self.group_ahead is not None:
+            stage_key, gfn, stage_ins = group
+            grouped, slot = self._ahead.run(self._graphs, stage_key, gfn, stage_ins, self.group_ahead,
+                                            vouched=getattr(self, "inputs_vouched", False))
+            key, head, n, ng = key + ("grouped",), list(carry), len(carry), len(grouped)
+        else:
+            grouped = slot = None
+            head, n, ng = list(inputs), len(inputs), 0
+        ins = head + list(grouped or ()) + list(masks or ())
+
+        def fn(*a):
+            m = a[n + ng:]
+            return (run(list(a[:n]), tuple(m) if m else None, list(a[n:n + ng]) if slot is not None else None),), None
+        (feat,), _ = self._graphs.get(key, lambda: GraphedCall(fn, ins))(*ins)
+        if slot is not None:
+            self._ahead.consumed(slot)
+        return feat.clone()
+
+
 _GROUP_STREAMS = {}
 
 
 def shared_group_stream(device=None):
     """The process-wide stream the grouping stage of the NEXT iteration runs on (FPS + kNN depend on the input cloud
-    only: point_encoder.PointTransformer._group_ahead).  Created once per GPU, like the text stream and for the same
+    only: AheadStage, which every point encoder runs its stage through).  Created once per GPU, like the text stream and for the same
     reason; callers that care about hardware-queue placement create it right after shared_text_stream()."""
     dev = torch.cuda.current_device() if device is None else torch.device(device).index
     if dev not in _GROUP_STREAMS:

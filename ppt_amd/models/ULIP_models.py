@@ -1041,7 +1041,7 @@ class ULIP_WITH_IMAGE(nn.Module):
                  and hasattr(pe, "group_ahead") and self.task != 'partseg')
         if ahead:
             # validate() with resident inputs (eval_inputs_ready): the next batch's FPS + kNN + tokenizer on the grouping stream,
-            # under this batch's blocks -- the same ahead stage train.Trainer uses (PointTransformer._group_ahead)
+            # under this batch's blocks -- the same ahead stage train.Trainer uses (graphs.AheadStage)
             pe.group_ahead = graphs.shared_group_stream()
             pe.inputs_vouched = bool(self.eval_inputs_ready)     # (else: only tensors that carry their copy event run ahead)
         try:

@@ -200,35 +200,45 @@ class _PointEncoderFn(torch.autograd.Function):
         has_dp = (train and module.drop_path_rate > 0) if drawn else dp is not None
         key = ("point_fwd", tuple(pc.shape), has_dp, drawn, train, cache.dtype, ops.get_persistent_occupancy() if pc.is_cuda else 100)
         ahead = module.group_ahead if (use_graph and module._graphs.ready(("group", tuple(pc.shape), drawn))) else None
-        if not split and use_graph and module._graphs.ready(key):
-            if ahead is not None:
-                # FPS + kNN (and, tokenize_ahead, the whole tokenizer) ran -- or run right now -- on the grouping stream,
-                # overlapping the previous iteration's blocks
-                tk = module.tokenize_ahead
-                grouped, slot = module._group_ahead(pc, fps_start, drawn, ahead, tokenize=tk)
-                ins = list(grouped) + ([dp] if dp is not None else [])
 
-                def build():
-                    def fn(nb_, ce_, *rest):
-                        dp_ = module._draw_drop_path(B, pc.device) if drawn else (rest[0] if rest else None)
-                        kw = dict(tokens=(nb_, ce_)) if tk else dict(grouped=(nb_, ce_))
-                        feat_, _ = engine.point_encoder_forward(sd, "", cache, None, None, dp_, train, 0, cfg, **kw)
-                        return (feat_,), None
-                    # (the tokens are handed over in place: one tower graph per ping-pong pair instead of 2 x 25 MB of copies)
-                    return graphs.GraphedCall(fn, ins, alias_inputs=tk and dp is None)
-                (feat,), _ = module._graphs.get(key + ((("tokens", slot) if dp is None else ("tokens",)) if tk else ("grouped",)), build)(*ins)
-                module._group_consumed(slot)
-                ctx.saved = None
-                return feat.clone()
-            ins = [pc] if drawn else [pc, fps_start] + ([dp] if dp is not None else [])
+        def section(source, stop):
+            """One captured section of the frozen tower -> (key suffix, inputs, GraphedCall factory, stage slot or None).
+            source "cloud": from (pc[, start][, dp]).  source "stage": from the pair the ahead stage hands over (+ dp) -- FPS + kNN
+            (and, tokenize_ahead, the whole tokenizer) run right now on the grouping stream, overlapping the previous iteration's blocks.
+            stop False: to the feature, outputs (feat,).  stop True: to the input of the last block, outputs (x2, pos2[, dp])."""
+            staged, tk = source == "stage", module.tokenize_ahead
+            slot, suffix, alias = None, (), False
+            if staged:
+                pair, slot = module._group_ahead(pc, fps_start, drawn, ahead, tokenize=tk)
+                ins = list(pair) + ([dp] if dp is not None else [])
+                # (the tokens are handed over in place: one tower graph per ping-pong pair instead of 2 x 25 MB of copies.  Not in
+                # front of a last block that trains: see the `split` branch)
+                alias = tk and dp is None and not stop
+                suffix = (("tokens", slot) if alias else ("tokens",)) if tk else ("grouped",)
+            else:
+                ins = [pc] if drawn else [pc, fps_start] + ([dp] if dp is not None else [])
 
-            def build():
-                def fn(pc_, *rest):
+            def fn(*a):
+                rest = a[2:] if staged else a[1:]
+                if staged:
+                    pc_ = start_ = None
+                    dp_ = module._draw_drop_path(B, pc.device) if drawn else (rest[0] if rest else None)
+                    kw = dict(tokens=a[:2]) if tk else dict(grouped=a[:2])
+                else:
+                    pc_, kw = a[0], {}
                     start_, dp_ = draw() if drawn else (rest[0], rest[1] if len(rest) > 1 else None)
-                    feat_, _ = engine.point_encoder_forward(sd, "", cache, pc_, start_, dp_, train, 0, cfg)
+                if not stop:
+                    feat_, _ = engine.point_encoder_forward(sd, "", cache, pc_, start_, dp_, train, 0, cfg, **kw)
                     return (feat_,), None
-                return graphs.GraphedCall(fn, ins)
-            (feat,), _ = module._graphs.get(key, build)(*ins)
+                x2_, pos2_ = engine.point_encoder_forward(sd, "", cache, pc_, start_, dp_, train, 0, cfg, last_block=False, **kw)
+                return (x2_, pos2_) + ((dp_,) if dp_ is not None else ()), None
+            return suffix, ins, lambda: graphs.GraphedCall(fn, ins, alias_inputs=alias), slot
+
+        if not split and use_graph and module._graphs.ready(key):
+            suffix, ins, build, slot = section("stage" if ahead is not None else "cloud", stop=False)
+            (feat,), _ = module._graphs.get(key + suffix, build)(*ins)
+            if slot is not None:
+                module._ahead.consumed(slot)
             ctx.saved = None
             return feat.clone()
         if split and pc.is_cuda:
@@ -237,38 +247,15 @@ class _PointEncoderFn(torch.autograd.Function):
             # set by train.Trainer.step) -- the prefix runs ahead of it like the whole tower does for head_type 0.
             key = ("point_prefix", tuple(pc.shape), has_dp, drawn, train, cache.dtype, ops.get_persistent_occupancy() if pc.is_cuda else 100)
             if use_graph and module._graphs.ready(key):
-                slot = None
-                if ahead is not None:
-                    tk = module.tokenize_ahead
-                    grouped, slot = module._group_ahead(pc, fps_start, drawn, ahead, tokenize=tk)
-                    ins = list(grouped) + ([dp] if dp is not None else [])
-
-                    def build():
-                        def fn(nb_, ce_, *rest):
-                            dp_ = module._draw_drop_path(B, pc.device) if drawn else (rest[0] if rest else None)
-                            kw = dict(tokens=(nb_, ce_)) if tk else dict(grouped=(nb_, ce_))
-                            x2_, pos2_ = engine.point_encoder_forward(sd, "", cache, None, None, dp_, train, 0, cfg,
-                                                                      last_block=False, **kw)
-                            return (x2_, pos2_) + ((dp_,) if dp_ is not None else ()), None
-                        # (NOT handed over in place here: the last block keeps activations for its backward, and they must not
-                        # live in the stage's ping-pong buffers -- the stage of a later step, which waits for the forward only,
-                        # would overwrite them before that backward has run.  Releasing the pair behind the backward instead was
-                        # measured: it costs the whole gain of the stage, C3 6.27 -> 6.59 ms; two 50 MB copies cost 35 us.)
-                        return graphs.GraphedCall(fn, ins)
-                    key = key + (("tokens",) if tk else ("grouped",))
-                else:
-                    ins = [pc] if drawn else [pc, fps_start] + ([dp] if dp is not None else [])
-
-                    def build():
-                        def fn(pc_, *rest):
-                            start_, dp_ = draw() if drawn else (rest[0], rest[1] if len(rest) > 1 else None)
-                            x2_, pos2_ = engine.point_encoder_forward(sd, "", cache, pc_, start_, dp_, train, 0, cfg, last_block=False)
-                            return (x2_, pos2_) + ((dp_,) if dp_ is not None else ()), None
-                        return graphs.GraphedCall(fn, ins)
-                g = module._graphs.get(key, build)
+                # (the stage's pair is NOT handed over in place here: the last block keeps activations for its backward, and they must
+                # not live in the stage's ping-pong buffers -- the stage of a later step, which waits for the forward only,
+                # would overwrite them before that backward has run.  Releasing the pair behind the backward instead was
+                # measured: it costs the whole gain of the stage, C3 6.27 -> 6.59 ms; two 50 MB copies cost 35 us.)
+                suffix, ins, build, slot = section("stage" if ahead is not None else "cloud", stop=True)
+                g = module._graphs.get(key + suffix, build)
                 outs, _ = g(*ins)
                 if slot is not None:
-                    module._group_consumed(slot)
+                    module._ahead.consumed(slot)
                 g.generation = getattr(g, "generation", 0) + 1
                 ctx.prefix_graph, ctx.prefix_generation = g, g.generation
                 cut, dp = (outs[0], outs[1]), (outs[2] if len(outs) > 2 else None)
@@ -346,8 +333,7 @@ class PointTransformer(nn.Module):
         # ... and with it the rest of the tokenizer (mini-PointNet, reduce_dim, pos_embed: frozen in every PPT configuration, a
         # function of the cloud alone, HBM-bound where the blocks it then runs beside are not).  PPT_TOKENIZE_AHEAD=0: FPS + kNN only.
         self.tokenize_ahead = os.environ.get("PPT_TOKENIZE_AHEAD", "1") != "0"
-        self._group_slot = 0
-        self._group_free = [None, None]
+        self._ahead = graphs.AheadStage()
         self.fps_start = None            # [B] int64: injected FPS start indices (else torch.randint)
         self.drop_path_factors = None    # [depth,2,B] fp32: injected DropPath factors (else drawn on device)
         self._wc = None
@@ -407,45 +393,24 @@ class PointTransformer(nn.Module):
         return in_last > 0, total > in_last
 
     def _group_ahead(self, pc, fps_start, drawn, side, tokenize=False):
-        """Group.forward (dvae.py:159-181) of `pc` on `side`, replayed from one of two hipGraphs with their own output
-        buffers (the previous tower may still be reading the other pair).  The caller's stream is made to wait for the
-        result; `side` waits for nothing but the tower that last read this pair -- NOT for the caller's stream, which is
-        the point: the caller guarantees `pc` (and `fps_start`) are complete in memory.  -> ((nbhd, center), slot).
+        """Group.forward (dvae.py:159-181) of `pc` as a graphs.AheadStage on `side` -> ((nbhd, center), slot); the caller releases
+        the slot with self._ahead.consumed(slot) once the tower that reads the pair is queued.
         tokenize: the stage runs the whole tokenizer (engine.tokenize_points: + mini-PointNet, reduce_dim, pos_embed -- frozen
         weights, train-mode BatchNorm statistics of this batch) -> ((x2, pos2), slot), the blocks' input."""
-        main = torch.cuda.current_stream()
-        slot = self._group_slot = (self._group_slot + 1) % len(self._group_free)
         B, N = pc.shape[0], pc.shape[1]
         G, n = self.num_group, self.group_size
-        ins = [pc] if drawn else [pc, fps_start]
-        key = ("group", tuple(pc.shape), drawn, slot)
+        key = ("group", tuple(pc.shape), drawn)
         if tokenize:
             sd, cache, cfg, train = self._live_state(), self._cache(), self._cfg(), self.training
-            key = ("tokens", tuple(pc.shape), drawn, train, cache.dtype, ops.get_persistent_occupancy(), slot)
+            key = ("tokens", tuple(pc.shape), drawn, train, cache.dtype, ops.get_persistent_occupancy())
 
-        def build():
-            def fn(pc_, *rest):
-                start_ = torch.randint(0, N, (B,), dtype=torch.long, device=pc_.device) if drawn else rest[0]   # misc.py:59
-                if tokenize:
-                    return tuple(engine.tokenize_points(sd, "", cache, pc_, start_, train, cfg)[:2]), None
-                return tuple(engine.group_points(pc_, G, n, start_)), None
-            return graphs.GraphedCall(fn, ins)
-        with torch.cuda.stream(side):
-            if self._group_free[slot] is not None:
-                side.wait_event(self._group_free[slot])
-            # (a DevicePrefetcher batch: behind its copy; a vouched-for tensor: nothing; a tensor DERIVED from the batch on the
-            # caller's stream, which no event covers: behind the caller's stream -- graphs.wait_inputs)
-            graphs.wait_inputs(side, ins, main, getattr(self, "inputs_vouched", False))
-            grouped, _ = self._graphs.get(key, build)(*ins)
-            done = side.record_event()
-        for t in ins:
-            t.record_stream(side)
-        main.wait_event(done)
-        return grouped, slot
-
-    def _group_consumed(self, slot):
-        """The tower reading pair `slot` has been queued on the current stream: the pair is free once it has run."""
-        self._group_free[slot] = torch.cuda.current_stream().record_event()
+        def fn(pc_, *rest):
+            start_ = torch.randint(0, N, (B,), dtype=torch.long, device=pc_.device) if drawn else rest[0]   # misc.py:59
+            if tokenize:
+                return tuple(engine.tokenize_points(sd, "", cache, pc_, start_, train, cfg)[:2]), None
+            return tuple(engine.group_points(pc_, G, n, start_)), None
+        return self._ahead.run(self._graphs, key, fn, [pc] if drawn else [pc, fps_start], side,
+                               vouched=getattr(self, "inputs_vouched", False))
 
     def _draw_drop_path(self, B, device):
         """timm DropPath factors for both residual branches of every block (train mode only)."""
@@ -681,8 +646,10 @@ class PointTransformer_partseg(nn.Module):
         injected = self.fps_start is not None or self.drop_path_factors is not None or self.dropout_mask is not None
         key = ("partseg_backbone", (B, N), self.training, self._precision)
         slot = None
-        if (pts.is_cuda and self.use_hip_graphs and graphs.enabled and ops.profiler is None and (not injected or self._graph_injected)
-                and not torch.cuda.is_current_stream_capturing() and self._graphs.ready(key)):
+        # may this forward replay hipGraphs at all (the backbone's here, the decoder's below)
+        may_graph = (pts.is_cuda and self.use_hip_graphs and graphs.enabled and ops.profiler is None
+                     and (not injected or self._graph_injected) and not torch.cuda.is_current_stream_capturing())
+        if may_graph and self._graphs.ready(key):
             if self.group_ahead is not None and self.backbone_ahead:
                 # ... and the WHOLE frozen backbone with it (round 3): tokenizer, the 12 blocks and the three feature taps are a
                 # function of the cloud, the frozen weights and RNG draws made inside the stage's graph -- nothing the optimizer
@@ -713,9 +680,7 @@ class PointTransformer_partseg(nn.Module):
                 torch.cuda.current_stream().wait_event(self.decoder_gate)
             self.decoder_gate = None
         dkey = ("partseg_decoder_warm", (B, N), self.training, self._precision)
-        if (pts.is_cuda and self.training and torch.is_grad_enabled() and self.use_hip_graphs and self.graph_decoder and graphs.enabled
-                and ops.profiler is None and (not injected or self._graph_injected) and not torch.cuda.is_current_stream_capturing()
-                and self._graphs.ready(dkey)):
+        if may_graph and self.training and torch.is_grad_enabled() and self.graph_decoder and self._graphs.ready(dkey):
             # the decoder's forward AND backward from hipGraphs, as one autograd node (ppt_amd.autograd._PartsegDecoder)
             from ...autograd import _PartsegDecoder, partseg_decoder_params
             drop = self.dropout_mask.to(dev) if self.dropout_mask is not None else None

@@ -74,7 +74,7 @@ class PosExtraction(nn.Module):
                                                          activation=activation) for _ in range(blocks)])
 
 
-class Model(nn.Module):
+class Model(graphs.FrozenTower, nn.Module):
     """pointMLP.py:285-334.  forward(x [B,N,3]) -> [B,256].
 
     Build-specific knobs: `precision` (bf16 / fp32 parity), `fps_start` = one start vector [B] per stage and
@@ -109,28 +109,8 @@ class Model(nn.Module):
                                         nn.Linear(512, 256), nn.BatchNorm1d(256), self.act, nn.Dropout(0.5))
         self._cfg = dict(points=points, k_neighbors=list(k_neighbors), reducers=list(reducers), pre_blocks=list(pre_blocks),
                          pos_blocks=list(pos_blocks))
-        self.precision = torch.bfloat16
-        self.fps_start = None
-        self.dropout_masks = None
-        self._wc = None
-        self._sd = None
-        self._graphs = graphs.GraphCache()
-        self.use_hip_graphs = True
-        self.group_ahead = None            # stream for the grouping stage of the next iteration (train.Trainer.inputs_ready)
+        self._init_tower()
         self.group_ahead_pays_when_frozen = True
-        self._ahead = graphs.AheadStage()
-
-    def _apply(self, fn, *a, **k):
-        self._sd = None
-        if hasattr(self, "_graphs"):
-            self._graphs.clear()
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._sd, self._wc = None, None
-        if hasattr(self, "_graphs"):
-            self._graphs.clear()
-        return super().load_state_dict(*a, **k)
 
     def load_model_from_ckpt(self, ckpt_path):
         """pointMLP.py:336-350."""
@@ -150,8 +130,7 @@ class Model(nn.Module):
         xyz = x.contiguous().float()
         B, N, _ = xyz.shape
         cfg = self._cfg
-        if self._wc is None or self._wc.dtype != self.precision:
-            self._wc = engine.WeightCache(self.precision)
+        sd, wc = self._state(self.embedding.net[0].weight)
         if self.precision == torch.float32:
             ops.set_split16(self.__dict__.get("split16", False))
         n_src, s = [N], cfg["points"]                                    # points FPS draws its start from, per stage
@@ -168,42 +147,22 @@ class Model(nn.Module):
         elif self.training:
             masks = ((torch.rand((B, 512), device=xyz.device) >= 0.5).float() * 2.0,
                      (torch.rand((B, 256), device=xyz.device) >= 0.5).float() * 2.0)
-        w0 = self.embedding.net[0].weight
-        if self._sd is None or self._sd[1] is not w0:
-            self._sd = (self.state_dict(keep_vars=True), w0)
-        sd, wc, train = self._sd[0], self._wc, self.training
-        ns = len(starts)
+        train = self.training
         with torch.no_grad():            # every parameter of this encoder is frozen in PPT (ULIP_models.py:425-439)
             key = ("pointmlp", tuple(xyz.shape), masks is not None, train, wc.dtype)
-            if xyz.is_cuda and self.use_hip_graphs and ops.profiler is None and self._graphs.ready(key):
-                if self.group_ahead is not None:
-                    # FPS + kNN of the four stages on the grouping stream (graphs.AheadStage); starts that are not injected
-                    # are drawn there too (the ones drawn above sit on the caller's stream, behind the previous step)
-                    drawn = self.fps_start is None
+            drawn = self.fps_start is None
 
-                    def gfn(x, *st):
-                        st = st if st else tuple(torch.randint(0, n, (B,), dtype=torch.long, device=x.device) for n in n_src)
-                        return tuple(engine.pointmlp_group(x, st, cfg)), None
-                    grouped, slot = self._ahead.run(self._graphs, ("pointmlp_group", tuple(xyz.shape), drawn), gfn,
-                                                    [xyz] + ([] if drawn else list(starts)), self.group_ahead, vouched=getattr(self, "inputs_vouched", False))
-                    ng = len(grouped)
-                    ins = [xyz] + list(grouped) + (list(masks) if masks is not None else [])
+            def gfn(x, *st):
+                # FPS + kNN of the four stages on the grouping stream (graphs.FrozenTower.dispatch); starts that are not injected
+                # are drawn there too (the ones drawn above sit on the caller's stream, behind the previous step)
+                st = st if st else tuple(torch.randint(0, n, (B,), dtype=torch.long, device=x.device) for n in n_src)
+                return tuple(engine.pointmlp_group(x, st, cfg)), None
 
-                    def fn2(x_, *a):
-                        m = a[ng:]
-                        return (engine.pointmlp_forward(sd, "", wc, x_, None, train, tuple(m) if m else None, cfg=cfg,
-                                                        grouped=list(a[:ng])),), None
-                    (feat,), _ = self._graphs.get(key + ("grouped",), lambda: graphs.GraphedCall(fn2, ins))(*ins)
-                    self._ahead.consumed(slot)
-                    return feat.clone()
-                ins = [xyz] + list(starts) + (list(masks) if masks is not None else [])
-
-                def fn(x_, *rest):
-                    m = rest[ns:]
-                    return (engine.pointmlp_forward(sd, "", wc, x_, rest[:ns], train, tuple(m) if m else None, cfg=cfg),), None
-                (feat,), _ = self._graphs.get(key, lambda: graphs.GraphedCall(fn, ins))(*ins)
-                return feat.clone()
-            return engine.pointmlp_forward(sd, "", wc, xyz, starts, train, masks, cfg=cfg)
+            def run(ins, m, grouped):
+                return engine.pointmlp_forward(sd, "", wc, ins[0], tuple(ins[1:]) if grouped is None else None, train, m, cfg=cfg,
+                                               grouped=grouped)
+            return self.dispatch(key, [xyz, *starts], masks, run, carry=[xyz],
+                                 group=(("pointmlp_group", tuple(xyz.shape), drawn), gfn, [xyz] if drawn else [xyz, *starts]))
 
 
 def pointMLP(**kwargs) -> Model:

@@ -5,7 +5,7 @@ forward runs ppt_amd.engine.pointnet2_msg_forward (FPS + ball query + grouped-ML
 import torch
 import torch.nn as nn
 
-from ... import engine, graphs, ops
+from ... import engine, graphs
 
 
 class PointNetSetAbstractionMsg(nn.Module):
@@ -46,7 +46,7 @@ class PointNetSetAbstraction(nn.Module):
         self.remove_last = remove_last
 
 
-class Pointnet2_Msg(nn.Module):
+class Pointnet2_Msg(graphs.FrozenTower, nn.Module):
     """pointnet2.py:40-73.  forward(xyz [B,N,3]) -> [B,256].
 
     Build-specific knobs: `precision` (bf16 / fp32 parity), `fps_start` = (start1 [B], start2 [B]) and
@@ -77,35 +77,14 @@ class Pointnet2_Msg(nn.Module):
         self.fc2 = nn.Linear(512, 256)
         self.bn2 = nn.BatchNorm1d(256)
         self.drop2 = nn.Dropout(0.5)
-        self.precision = torch.bfloat16
-        self.fps_start = None
-        self.dropout_masks = None
-        self._wc = None
-        self._sd = None
-        self._graphs = graphs.GraphCache()
-        self.use_hip_graphs = True
-        self.group_ahead = None            # stream for the grouping stage of the next iteration (train.Trainer.inputs_ready)
-        self._ahead = graphs.AheadStage()
-
-    def _apply(self, fn, *a, **k):
-        self._sd = None
-        if hasattr(self, "_graphs"):
-            self._graphs.clear()
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._sd, self._wc = None, None
-        if hasattr(self, "_graphs"):
-            self._graphs.clear()
-        return super().load_state_dict(*a, **k)
+        self._init_tower()
 
     def forward(self, xyz, lengths=None):
         xyz = xyz.contiguous().float()
         B, N, _ = xyz.shape
         if lengths is not None:
             lengths = engine.cloud_lengths(lengths, B, N, xyz.device)
-        if self._wc is None or self._wc.dtype != self.precision:
-            self._wc = engine.WeightCache(self.precision)
+        sd, wc = self._state(self.fc1.weight)
         if self.fps_start is not None:
             starts = tuple(s.to(xyz.device).contiguous() for s in self.fps_start)
         else:
@@ -119,47 +98,29 @@ class Pointnet2_Msg(nn.Module):
             p1, p2 = self._drop_p
             masks = ((torch.rand((B, 512), device=xyz.device) >= p1).float() / (1.0 - p1),
                      (torch.rand((B, 256), device=xyz.device) >= p2).float() / (1.0 - p2))
-        if self._sd is None or self._sd[1] is not self.fc1.weight:
-            self._sd = (self.state_dict(keep_vars=True), self.fc1.weight)
-        sd, wc, train = self._sd[0], self._wc, self.training
+        train, fwd, levels = self.training, self._engine_forward, self._group_levels
         with torch.no_grad():            # every parameter of this encoder is frozen in PPT (ULIP_models.py:372-389)
-            # ~90 shape-static launches: replayed from a hipGraph after graphs.WARMUP_CALLS eager calls (ppt_amd/graphs.py)
-            key = (self._graph_tag, tuple(xyz.shape), masks is not None, train, wc.dtype)
-            fwd = self._engine_forward
             if lengths is not None:
-                grouped = engine.pointnet2_group(xyz, starts, self._group_levels, lengths=lengths)
+                grouped = engine.pointnet2_group(xyz, starts, levels, lengths=lengths)
                 return fwd(sd, "", wc, None, None, train, masks, grouped=grouped)
-            if xyz.is_cuda and self.use_hip_graphs and ops.profiler is None and self._graphs.ready(key):
-                if self.group_ahead is not None:
-                    # FPS + ball queries of both levels on the grouping stream (graphs.AheadStage), the rest from here
-                    levels = self._group_levels
-                    drawn = self.fps_start is None
-                    n1 = levels[0][0]
+            # ~90 shape-static launches: replayed from a hipGraph after graphs.WARMUP_CALLS eager calls; with `group_ahead`, FPS + ball
+            # queries of both levels on the grouping stream and the rest from here (graphs.FrozenTower.dispatch)
+            key = (self._graph_tag, tuple(xyz.shape), masks is not None, train, wc.dtype)
+            drawn = self.fps_start is None
 
-                    def gfn(x, *st):
-                        # not injected: the two FPS starts are drawn here, on the grouping stream (the ones drawn above sit on
-                        # the caller's stream, behind the previous tower)
-                        s0, s1 = st if st else (torch.randint(0, N, (B,), dtype=torch.long, device=x.device),
-                                                torch.randint(0, n1, (B,), dtype=torch.long, device=x.device))
-                        return tuple(engine.pointnet2_group(x, (s0, s1), levels)), None
-                    grouped, slot = self._ahead.run(self._graphs, ("pn2_group", tuple(xyz.shape), drawn), gfn,
-                                                    [xyz] + ([] if drawn else [starts[0], starts[1]]), self.group_ahead, vouched=getattr(self, "inputs_vouched", False))
-                    ng = len(grouped)
-                    ins = list(grouped) + (list(masks) if masks is not None else [])
+            def gfn(x, *st):
+                # not injected: the two FPS starts are drawn here, on the grouping stream (the ones drawn above sit on
+                # the caller's stream, behind the previous tower)
+                st = st if st else (torch.randint(0, N, (B,), dtype=torch.long, device=x.device),
+                                    torch.randint(0, levels[0][0], (B,), dtype=torch.long, device=x.device))
+                return tuple(engine.pointnet2_group(x, st, levels)), None
 
-                    def fn2(*a):
-                        m = a[ng:]
-                        return (fwd(sd, "", wc, None, None, train, tuple(m) if m else None, grouped=list(a[:ng])),), None
-                    (feat,), _ = self._graphs.get(key + ("grouped",), lambda: graphs.GraphedCall(fn2, ins))(*ins)
-                    self._ahead.consumed(slot)
-                    return feat.clone()
-                ins = [xyz, starts[0], starts[1]] + (list(masks) if masks is not None else [])
-
-                def fn(x, s0, s1, *m):
-                    return (fwd(sd, "", wc, x, (s0, s1), train, tuple(m) if m else None),), None
-                (feat,), _ = self._graphs.get(key, lambda: graphs.GraphedCall(fn, ins))(*ins)
-                return feat.clone()
-            return fwd(sd, "", wc, xyz, starts, train, masks)
+            def run(ins, m, grouped):
+                if grouped is not None:
+                    return fwd(sd, "", wc, None, None, train, m, grouped=grouped)
+                return fwd(sd, "", wc, ins[0], tuple(ins[1:]), train, m)
+            return self.dispatch(key, [xyz, *starts], masks, run,
+                                 group=(("pn2_group", tuple(xyz.shape), drawn), gfn, [xyz] if drawn else [xyz, *starts]))
 
 
 class Pointnet2_Ssg(Pointnet2_Msg):
@@ -186,12 +147,4 @@ class Pointnet2_Ssg(Pointnet2_Msg):
         self.fc2 = nn.Linear(512, 256)
         self.bn2 = nn.BatchNorm1d(256)
         self.drop2 = nn.Dropout(0.4)
-        self.precision = torch.bfloat16
-        self.fps_start = None
-        self.dropout_masks = None
-        self._wc = None
-        self._sd = None
-        self._graphs = graphs.GraphCache()
-        self.use_hip_graphs = True
-        self.group_ahead = None            # stream for the grouping stage of the next iteration (train.Trainer.inputs_ready)
-        self._ahead = graphs.AheadStage()
+        self._init_tower()

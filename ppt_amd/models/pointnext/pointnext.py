@@ -63,7 +63,7 @@ class ClsHead(nn.Module):
         self.head = nn.Sequential(*heads)
 
 
-class BaseCls(nn.Module):
+class BaseCls(graphs.FrozenTower, nn.Module):
     """classification/cls_base.py:12-32.  forward(pc [B,N,4] = (x, y, z, height)) -> [B,256].
 
     Build-specific knobs, as on Pointnet2_Msg: `precision` (torch.bfloat16 = the 16-bit performance mode, whose operand format is
@@ -75,26 +75,7 @@ class BaseCls(nn.Module):
         super().__init__()
         self.encoder = PointNextEncoder()
         self.prediction = ClsHead(self.encoder.out_channels)
-        self.precision = torch.bfloat16
-        self.dropout_masks = None
-        self._wc = None
-        self._sd = None
-        self._graphs = graphs.GraphCache()
-        self.use_hip_graphs = True
-        self.group_ahead = None            # stream for the grouping stage of the next iteration (train.Trainer.inputs_ready)
-        self._ahead = graphs.AheadStage()
-
-    def _apply(self, fn, *a, **k):
-        self._sd = None
-        if hasattr(self, "_graphs"):
-            self._graphs.clear()
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._sd, self._wc = None, None
-        if hasattr(self, "_graphs"):
-            self._graphs.clear()
-        return super().load_state_dict(*a, **k)
+        self._init_tower(fps_start=False)  # (FPS starts at index 0 here: nothing to inject)
 
     def _operand_dtype(self):
         if self.precision == torch.bfloat16 and engine.POINTNEXT_F16:
@@ -111,8 +92,7 @@ class BaseCls(nn.Module):
         pc = pc.contiguous().float()
         B = pc.shape[0]
         T = self._operand_dtype()
-        if self._wc is None or self._wc.dtype != T:
-            self._wc = engine.WeightCache(T)
+        sd, wc = self._state(self.encoder.encoder[0][0].convs[0][0].weight, T)
         if T == torch.float32:
             # (a 16-bit encoder leaves the process-wide switch to its owner's text tower, whose backward still reads it; its own
             # fp32 coordinate GEMMs say `split=False` themselves: engine._pointnext_level)
@@ -122,36 +102,17 @@ class BaseCls(nn.Module):
             masks = tuple(m.to(device=pc.device, dtype=torch.float32).contiguous() for m in self.dropout_masks)
         elif self.training:
             masks = tuple((torch.rand((B, w), device=pc.device) >= 0.5).float() * 2.0 for w in HEAD_MLPS)
-        w0 = self.encoder.encoder[0][0].convs[0][0].weight
-        if self._sd is None or self._sd[1] is not w0:
-            self._sd = (self.state_dict(keep_vars=True), w0)
-        sd, wc, train = self._sd[0], self._wc, self.training
-        fwd = engine.pointnext_forward
+        train = self.training
         with torch.no_grad():            # every parameter of this encoder is frozen in PPT (ULIP_models.py:572-618)
             key = ("pointnext", tuple(pc.shape), masks is not None, train, wc.dtype, bool(self.__dict__.get("split16", False)))
-            if pc.is_cuda and self.use_hip_graphs and ops.profiler is None and self._graphs.ready(key):
-                if self.group_ahead is not None:
-                    # the four FPS + ball queries on the grouping stream (graphs.AheadStage), the rest from here
-                    def gfn(x):
-                        return tuple(engine.pointnext_group(x[..., :3].contiguous())), None
-                    grouped, slot = self._ahead.run(self._graphs, ("pointnext_group", tuple(pc.shape)), gfn, [pc], self.group_ahead,
-                                                    vouched=getattr(self, "inputs_vouched", False))
-                    ng = len(grouped)
-                    ins = [pc] + list(grouped) + (list(masks) if masks is not None else [])
 
-                    def fn2(x, *a):
-                        m = a[ng:]
-                        return (fwd(sd, "", wc, x, train, tuple(m) if m else None, grouped=list(a[:ng])),), None
-                    (feat,), _ = self._graphs.get(key + ("grouped",), lambda: graphs.GraphedCall(fn2, ins))(*ins)
-                    self._ahead.consumed(slot)
-                    return feat.clone()
-                ins = [pc] + (list(masks) if masks is not None else [])
+            def gfn(x):
+                # the four FPS + ball queries on the grouping stream, the rest from here (graphs.FrozenTower.dispatch)
+                return tuple(engine.pointnext_group(x[..., :3].contiguous())), None
 
-                def fn(x, *m):
-                    return (fwd(sd, "", wc, x, train, tuple(m) if m else None),), None
-                (feat,), _ = self._graphs.get(key, lambda: graphs.GraphedCall(fn, ins))(*ins)
-                return feat.clone()
-            return fwd(sd, "", wc, pc, train, masks)
+            def run(ins, m, grouped):
+                return engine.pointnext_forward(sd, "", wc, ins[0], train, m, grouped=grouped)
+            return self.dispatch(key, [pc], masks, run, carry=[pc], group=(("pointnext_group", tuple(pc.shape)), gfn, [pc]))
 
 
 def PointNEXT():

@@ -281,7 +281,7 @@ class Trainer:
         # True: the caller vouches that `pc` is complete in device memory when step() is called (a resident tensor, or a
         # loader that synchronised its copy stream) -- NOT merely queued on the current stream.  The grouping stage of the
         # point tower (FPS + kNN, a function of pc alone) then runs on its own stream as soon as step() is called, i.e.
-        # under the previous iteration's transformer blocks (models/pointbert/point_encoder.py: _group_ahead).
+        # under the previous iteration's transformer blocks (graphs.AheadStage, which every point encoder runs its stage through).
         self.inputs_ready = False
         # head_type 0 with inputs_ready: the frozen point tower of iteration i + 1 does not wait for iteration i's head (which
         # waits for the prompt chain) -- it runs on its own stream, back to back (ULIP_WITH_IMAGE.forward_loss).  Opt-in: it
