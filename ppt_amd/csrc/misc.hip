@@ -8,6 +8,16 @@ namespace {
 // flight per wave (with 4 waves and one load at a time the 513-token walk was latency: 38 us on the tail of the tower);
 // the partial (max, first index) pairs fold through LDS with torch.max's first-maximum rule.
 constexpr int CMP_W = 16;
+constexpr int CMP_NONE = 0x7fffffff;        // index of a wave that has seen no token yet (best = -inf); never written: token 1 is wave 0's
+
+// torch.max's order: NaN is the maximum, and of equal candidates the lowest token wins.  (v, i) against the best so far -- also
+// against the (-inf, CMP_NONE) start, which a -inf token replaces: a column of -inf gives token 1, one of NaN its first NaN.
+__device__ __forceinline__ bool cmp_takes(float v, int i, float best, int besti)
+{
+    if (best != best) return v != v && i < besti;
+    return v != v || v > best || (v == best && i < besti);
+}
+
 template <typename TX>
 __global__ __launch_bounds__(CMP_W * 64) void cls_max_pool_kernel(const TX *__restrict__ x, int T, int D, float *__restrict__ out,
                                                                   int32_t *__restrict__ argmax)
@@ -17,7 +27,7 @@ __global__ __launch_bounds__(CMP_W * 64) void cls_max_pool_kernel(const TX *__re
     const int b = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int d = blockIdx.x * 64 + lane;
     float best = -INFINITY;
-    int besti = 0x7fffffff;
+    int besti = CMP_NONE;
     if (d < D) {
         const TX *xb = x + (size_t)b * T * D + d;
         int t = 1 + w;
@@ -27,11 +37,11 @@ __global__ __launch_bounds__(CMP_W * 64) void cls_max_pool_kernel(const TX *__re
             for (int k = 0; k < 4; ++k) v[k] = dt<TX>::load(xb + (size_t)(t + k * CMP_W) * D);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (v[k] > best) { best = v[k]; besti = t + k * CMP_W; }
+                if (cmp_takes(v[k], t + k * CMP_W, best, besti)) { best = v[k]; besti = t + k * CMP_W; }
         }
         for (; t < T; t += CMP_W) {
             const float v = dt<TX>::load(xb + (size_t)t * D);
-            if (v > best) { best = v; besti = t; }
+            if (cmp_takes(v, t, best, besti)) { best = v; besti = t; }
         }
     }
     bv[w][lane] = best; bi[w][lane] = besti;
@@ -40,7 +50,7 @@ __global__ __launch_bounds__(CMP_W * 64) void cls_max_pool_kernel(const TX *__re
         for (int k = 1; k < CMP_W; ++k) {
             const float v = bv[k][lane];
             const int i = bi[k][lane];
-            if (v > best || (v == best && i < besti)) { best = v; besti = i; }
+            if (cmp_takes(v, i, best, besti)) { best = v; besti = i; }
         }
         out[(size_t)b * 2 * D + d] = dt<TX>::load(x + (size_t)b * T * D + d);
         out[(size_t)b * 2 * D + D + d] = best;
